@@ -1,6 +1,6 @@
 """bench.py -- train tokens/s (query+passage) of the CaSE model on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,7 +16,16 @@ the GPU the parent spawns `python -m torch.distributed.run --nproc-per-node N be
 JSON line and exits with the child's code (it never initialises the GPU).  The line carries `world_size` as
 `dist.get_world_size()` reports it and every rank's own step time.
 
-Extra objects in the JSON line:
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs is given and prints the
+line.  Everything else the benchmark measures runs only with --full: the objects below, and in decode mode the one-token pass that
+splits the step into its phases (``phases`` and ``roofline``).
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32; float64 for the losses), at
+most 64 MB in all.  Train modes: ``losses`` (the step's loss values) and ``params`` (a fixed, seeded sample of every parameter
+after the step).  Decode mode: every tensor the model returns;
+encoder mode: the encoder's output and state.  An array longer than DUMP_SAMPLE elements is cut to a fixed, seeded sample of its elements.
+
+Extra objects in the JSON line (--full only):
   roofline      dominant kernel family (the bf16 MFMA GEMM instantiation with the largest total time): algorithmic
                 FLOPs per launch / average launch duration, both measured live with HIP events on the launch stream
                 over one instrumented step after the timed region; peak = 2516.6 TFLOP/s dense bf16.
@@ -45,8 +54,11 @@ PEAK_BF16_TFLOPS = 2516.6  # 256 CU x 2.4 GHz x 4096 flop/clk/CU (MI355X_MICROAR
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=8)
+    ap.add_argument("--steps", type=int, default=8, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true", help="also run the measurements beyond the timed steps: roofline, north-star and decode "
+                                                        "points, CPU baseline, decode phase split")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=32, help="per-GPU batch (BASELINE cfg 2: 32)")
     ap.add_argument("--hidden", type=int, default=512)
     ap.add_argument("--enc-layers", type=int, default=6, help="BASELINE cfg 2 says 6; the reference hard-codes 3")
@@ -76,7 +88,12 @@ def parse():
     ap.add_argument("--graph", action="store_true", help="decode: replay the whole greedy pass from one captured hipGraph; train modes: replay the "
                                                          "training step from a hipGraph recorded after three untimed eager steps (CumulativeTrainer(capture=True): "
                                                          "dropout base / LR / Adam scalars in device memory, new masks on every replay)")
-    return ap.parse_args()
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not a.full:
+        a.no_cpu_baseline = a.no_roofline = a.no_north_star = a.no_decode_point = True
+    return a
 
 
 def forward_flops(a):
@@ -439,6 +456,21 @@ def decode_measure(a, device, world, rank):
         t = torch.tensor([elapsed], device=device, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if a.dump_outputs is not None and rank == 0:
+        dump_outputs(a.dump_outputs, out)
+    res = {
+        "metric": "decode answers/sec (CaSE greedy)", "value": round(world * a.batch * a.steps / elapsed, 2), "unit": "answers/s",
+        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 2),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
+        "config": {"workload": "CaSE greedy decode (encode + %d KV-cached steps), d_model=%d, %d encoder layers, %d passages x %d tok, "
+                               "per-GPU batch %d%s" % (a.decode_len, a.hidden, a.enc_layers, a.passages, a.passage_len, a.batch,
+                                                       ", hipGraph replay" if a.graph else ""),
+                   "global_batch": world * a.batch, "parallelism": "dp%d" % world},
+        "answer_sample": out["answer"][0, :8].tolist(),
+        "world_size": dist.get_world_size() if dist.is_initialized() else 1,
+    }
+    if not a.full:
+        return res
     # phase split (rank 0): the same batch with a ONE-token answer = encode + projections of the memories + one cached step;
     # the cached step itself = (T-token pass - 1-token pass) / (T - 1)
     S, H, T = a.passages * a.passage_len + a.query_len, a.hidden, a.decode_len
@@ -468,14 +500,7 @@ def decode_measure(a, device, world, rank):
     Sp, Lq = a.passages * a.passage_len, a.query_len
     moved_item_step = (4 * Sp * H + 4 * 2 * Lq * H + 2 * (Sp + Lq) * H) * 2
     moved_gbps = moved_item_step * a.batch / step_s / 1e9
-    res = {
-        "metric": "decode answers/sec (CaSE greedy)", "value": round(world * a.batch * a.steps / elapsed, 2), "unit": "answers/s",
-        "n_gpus": world, "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(elapsed / a.steps * 1e3, 2),
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": a.dtype, "data": "synthetic",
-        "config": {"workload": "CaSE greedy decode (encode + %d KV-cached steps), d_model=%d, %d encoder layers, %d passages x %d tok, "
-                               "per-GPU batch %d%s" % (T, H, a.enc_layers, a.passages, a.passage_len, a.batch, ", hipGraph replay" if a.graph else ""),
-                   "global_batch": world * a.batch, "parallelism": "dp%d" % world},
-        "answer_sample": out["answer"][0, :8].tolist(),
+    res.update({
         "phases": {"encode_plus_first_step_ms": round(one * 1e3, 2), "ms_per_cached_step": round(step_s * 1e3, 3),
                    "cached_steps": T - 1},
         "roofline": {"bound": "hbm", "kernel": "KV-cached greedy step (cross-attention K/V + additive-attention key streams)",
@@ -484,13 +509,13 @@ def decode_measure(a, device, world, rank):
                      "moved_bytes_per_step": moved_item_step * a.batch, "moved_gbps": round(moved_gbps, 1), "moved_frac": round(moved_gbps / 8000.0, 4),
                      "note": "achieved / frac price the step against SURVEY 8d's algorithm (K + V of four layers per memory + the additive keys); moved_* "
                              "against the bytes this implementation streams (absorbed cross-attention: one stream per layer; + the pointer context's value rows)"},
-        "world_size": dist.get_world_size() if dist.is_initialized() else 1,
-    }
+    })
     return res
 
 
 def encoder_point(a, device, batch=None, steps=None, warmup=None):
-    """North-star point: CaSE encoder forward, B x P x Lp tokens; returns (seconds per forward, algorithmic FLOPs)."""
+    """North-star point: CaSE encoder forward, B x P x Lp tokens; returns (seconds per forward, algorithmic FLOPs, the last
+    forward's output)."""
     import case_rg_amd
     from case_rg_amd.common.CumulativeTrainer import init_params
     from case_rg_amd.common.TransformerSeqEncoderDecoder import TransformerSeqEncoder
@@ -507,15 +532,17 @@ def encoder_point(a, device, batch=None, steps=None, warmup=None):
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         for _ in range(steps):
-            enc(ids)
+            out = enc(ids)
         torch.cuda.synchronize()
     dt = (time.perf_counter() - t0) / steps
     L, H, n = a.passage_len, a.hidden, batch * a.passages
-    return dt, a.enc_layers * n * (12 * L * H * H + 4 * L * L * H)
+    return dt, a.enc_layers * n * (12 * L * H * H + 4 * L * L * H), out
 
 
 def encoder_main(a, device):
-    dt, flops = encoder_point(a, device)
+    dt, flops, out = encoder_point(a, device)
+    if a.dump_outputs is not None:
+        dump_outputs(a.dump_outputs, {"encoder_output": out[0], "encoder_state": out[1]})
     L, H, n = a.passage_len, a.hidden, a.batch * a.passages
     emit({"metric": "CaSE encoder forward (north-star point)", "value": round(n * L / dt, 1), "unit": "tokens/s", "n_gpus": 1,
                       "steps": a.steps, "warmup": a.warmup, "ms_per_step": round(dt * 1e3, 3), "higher_is_better": True, "dtype": a.dtype,
@@ -528,7 +555,7 @@ def encoder_main(a, device):
 def north_star_point(a, device):
     """The target point of BASELINE.json (encoder forward at batch 64 x 10 passages x 384 tokens, bf16, eval mode), measured in
     the default run so that the driver's own bench line carries it."""
-    dt, flops = encoder_point(a, device, batch=64, steps=10, warmup=2)
+    dt, flops, _ = encoder_point(a, device, batch=64, steps=10, warmup=2)
     return {"workload": "TransformerSeqEncoder forward, %d layers, d_model %d, 64 x %d x %d tokens, bf16, eval" % (
                 a.enc_layers, a.hidden, a.passages, a.passage_len),
             "batch": 64, "layers": a.enc_layers, "ms": round(dt * 1e3, 3), "tflops": round(flops / dt / 1e12, 1),
@@ -553,6 +580,42 @@ def spawn_ranks(a):
     env.setdefault("OMP_NUM_THREADS", "8")
     proc = subprocess.run(cmd, env=env)
     raise SystemExit(proc.returncode)
+
+
+DUMP_SAMPLE = 1 << 20  # elements kept of a longer output array (4 MB in float32)
+DUMP_PER_PARAM = 4096  # elements sampled from each parameter tensor
+DUMP_SEED = 20241016
+
+
+def param_sample(model):
+    """A fixed, seeded sample of every parameter (named_parameters order, at most DUMP_PER_PARAM elements each), as one f32 vector on
+    the device.  The indices depend only on the parameter shapes, so two runs of the same arguments sample the same elements."""
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    parts = []
+    for _, p in model.named_parameters():
+        flat = p.detach().reshape(-1)
+        if flat.numel() > DUMP_PER_PARAM:
+            flat = flat[torch.randint(flat.numel(), (DUMP_PER_PARAM,), generator=g).to(flat.device)]
+        parts.append(flat.float())
+    return torch.cat(parts)
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: each array as <path>/<name>.npy, float64 kept as float64 and everything else as float32; an array of more than
+    DUMP_SAMPLE elements is cut to a fixed, seeded sample of its flattened elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    total = 0
+    for name, t in arrays.items():
+        t = torch.as_tensor(t).detach().reshape(-1)
+        if t.numel() > DUMP_SAMPLE:
+            g = torch.Generator().manual_seed(DUMP_SEED)
+            t = t[torch.randint(t.numel(), (DUMP_SAMPLE,), generator=g).to(t.device)]
+        arr = (t.double() if t.dtype == torch.float64 else t.float()).cpu().numpy()
+        total += arr.nbytes
+        if total > 64 << 20:
+            raise SystemExit("bench.py --dump-outputs: more than 64 MB of outputs")
+        np.save(os.path.join(path, name + ".npy"), arr)
 
 
 _REAL_STDOUT = None
@@ -618,7 +681,7 @@ def main():
         # 160 in the 5H blocks -- what "drops into Run.py unchanged" lands on.  Reported like the training line; no roofline object.
         a.hidden, a.passages, a.passage_len, a.query_len, a.answer_len, a.enc_layers = 256, 10, 100, 60, 40, 3
         a.batch = 16 if a.batch == 32 else a.batch
-        a.no_roofline, a.no_north_star, a.no_cpu_baseline, a.mode = not os.environ.get("CASE_BENCH_SHAPES"), True, True, "train"  # (the per-shape tuning table rides on the roofline pass)
+        a.no_roofline, a.no_north_star, a.no_cpu_baseline, a.mode = not (a.full and os.environ.get("CASE_BENCH_SHAPES")), True, True, "train"  # (the per-shape tuning table rides on the roofline pass)
         a.refdefault = True
     if a.mode == "decode":
         decode_main(a, device, world, rank)
@@ -658,6 +721,8 @@ def main():
         losses = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs is not None and rank == 0:
+        dump_outputs(a.dump_outputs, {"losses": torch.tensor(losses, dtype=torch.float64), "params": param_sample(trainer.model)})
     rank_ms = [round(elapsed / a.steps * 1e3, 2)]
     if world > 1:
         every = [torch.zeros(1, device=device, dtype=torch.float64) for _ in range(world)]

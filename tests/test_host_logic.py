@@ -136,15 +136,36 @@ def test_install_dropin_standalone_aliases_whole_packages():
                            "case_rg_amd.common.Utils"]
 
 
-REF = "/root/reference"
+# A stand-in for the reference tree: the package layout and the names its Run.py imports (CaSE/Run.py:1-11, Masque/Run.py:1-11), with
+# bodies of its own.  The hot-path modules raise when imported, so a name install_dropin() fails to alias cannot go unnoticed.
+_HOT = "raise ImportError('stand-in hot-path module: install_dropin() must alias it')\n"
+_STANDIN = {
+    "CaSE/CaSEDataset.py": "class CaSEDataset:\n    pass\n\n\ndef collate_fn(data):\n    return data\n",
+    "CaSE/Model.py": _HOT,
+    "Masque/MasqueDataset.py": "class MasqueDataset:\n    pass\n\n\ndef collate_fn(data):\n    return data\n",
+    "Masque/Model.py": _HOT,
+    "common/__init__.py": "",
+    "common/Constants.py": "PAD_WORD = '[PAD]'\nBOS_WORD = '[CLS]'\nEOS_WORD = '[SEP]'\nUNK_WORD = '[UNK]'\n",
+    "common/Utils.py": ("import torch\n\n\ndef bert_tokenizer(text):\n    return text.split()\n\n\ndef bert_detokenizer(tokens):\n"
+                        "    return ' '.join(tokens)\n\n\ndef topk(gen_output, k=5, PAD=None, BOS=None, UNK=None):\n"
+                        "    return torch.topk(gen_output, k, dim=1)\n\n\ndef build_map(b_map, max=None):\n    raise NotImplementedError\n\n\n"
+                        "def init_seed(seed):\n    raise NotImplementedError\n"),
+    "common/Generations.py": "from common.Utils import *\n\n\ndef greedy(model, data, vocab2id, max_len=20):\n    raise NotImplementedError\n",
+    "Utils.py": "from common.Utils import *\n\n\ndef save_result(predictions, dataset, output_path):\n    raise NotImplementedError\n",
+}
+_STANDIN.update({"common/%s.py" % m: _HOT for m in ("TransformerBlock", "Interaction", "CumulativeTrainer", "TransformerSeqEncoderDecoder")})
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="build container only: needs the reference tree (never on the GPU box)")
 @pytest.mark.parametrize("model", ["CaSE", "Masque"])
-def test_install_dropin_under_the_reference_run_py_imports(model):
+def test_install_dropin_under_the_reference_run_py_imports(model, tmp_path):
     """the import sequence of CaSE/Run.py:1-11 (Masque/Run.py:1-11) with install_dropin() in front,
-    under the SURVEY 8(c) stubs for the three third-party modules this container lacks.  The reference's own dataset,
-    tokenizer and result-writer names must keep resolving to ITS tree; the model, trainer and on-path helpers to the HIP path."""
+    under the SURVEY 8(c) stubs for the three third-party modules the reference needs, against a stand-in tree with the
+    reference's layout.  The tree's own dataset, tokenizer and result-writer names must keep resolving to ITS modules; the
+    model, trainer and on-path helpers to the HIP path."""
+    for rel, text in _STANDIN.items():
+        (tmp_path / rel).parent.mkdir(parents=True, exist_ok=True)
+        (tmp_path / rel).write_text(text)
+    REF = str(tmp_path)
     ds = {"CaSE": "CaSEDataset", "Masque": "MasqueDataset"}[model]
     out = _run_py("""
         import sys, types, importlib.machinery, math, torch
@@ -230,6 +251,40 @@ def test_bench_flop_model_matches_the_survey():
     assert bench.forward_flops(a) / 1e12 == pytest.approx(20.06, rel=0.03)
     a.enc_layers = 6
     assert bench.forward_flops(a) / 1e12 == pytest.approx(21.53, rel=0.03)
+
+
+
+def test_bench_plain_run_is_lean_and_full_keeps_the_extras(monkeypatch):
+    """A plain run measures the timed steps only; --full turns the roofline, north-star, decode-point and CPU-baseline legs back on
+    (each still switched off by its --no-* flag); --steps below 1 is refused."""
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "3"])
+    a = bench.parse()
+    assert a.steps == 3 and not a.full and a.dump_outputs is None
+    assert a.no_roofline and a.no_north_star and a.no_decode_point and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--no-cpu-baseline"])
+    a = bench.parse()
+    assert not (a.no_roofline or a.no_north_star or a.no_decode_point) and a.no_cpu_baseline
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_writes_fixed_samples(tmp_path):
+    """--dump-outputs: float64 stays float64, everything else becomes float32, and a long array or parameter is cut to the same
+    seeded sample in every run."""
+    import bench
+    model = torch.nn.Sequential(torch.nn.Linear(200, 100), torch.nn.Linear(100, 3))
+    s1, s2 = bench.param_sample(model), bench.param_sample(model)
+    assert torch.equal(s1, s2) and s1.numel() == bench.DUMP_PER_PARAM + 100 + 300 + 3
+    big = torch.arange(bench.DUMP_SAMPLE + 10, dtype=torch.float32).bfloat16()
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"losses": torch.tensor([1.5, 2.5], dtype=torch.float64), "params": s1, "big": big,
+                                               "ids": torch.arange(5)})
+    for name, dtype, n in (("losses", np.float64, 2), ("params", np.float32, s1.numel()), ("big", np.float32, bench.DUMP_SAMPLE),
+                           ("ids", np.float32, 5)):
+        x, y = np.load(tmp_path / "a" / (name + ".npy")), np.load(tmp_path / "b" / (name + ".npy"))
+        assert x.dtype == dtype and x.shape == (n,) and np.array_equal(x, y), name
 
 
 def test_split_k_heuristic_fills_whole_rounds():
