@@ -67,7 +67,8 @@ class CumulativeTrainer(object):
             from ..stepgraph import StepGraphs
             from ..stepstate import StepState
             self.step_state = StepState(next(self.model.parameters()).device)
-            config.set_device_state(self.step_state.address)  # every dropout site from here on adds the device-resident base
+            # every dropout site from here on adds the device-resident base (detached again by close(), or when the state is collected)
+            config.set_device_state(self.step_state.address, owner=self.step_state)
             self.graphs = StepGraphs(self, auto=capture == "auto")  # "auto": a capture is kept only where its replay is faster than the eager step
 
     def close(self):

@@ -11,9 +11,11 @@ dropout
     storing it, and DP replicas with the same seed/step agree.  Parity tests switch dropout off
     (``set_dropout(False)``) because torch's RNG stream cannot be reproduced; bench.py keeps it on.
 """
+import weakref
+
 import torch
 
-_state = {"dtype": torch.float32, "dropout": True, "seed": 123456, "offset": 0, "base": 0, "device_state": None}
+_state = {"dtype": torch.float32, "dropout": True, "seed": 123456, "offset": 0, "base": 0, "device_state": None, "device_token": None}
 
 
 def set_compute_dtype(dtype):
@@ -77,15 +79,30 @@ def next_rng(numel):
     return _state["seed"], off, _state["device_state"]
 
 
-def set_device_state(address):
+def set_device_state(address, owner=None):
     """Address of the CaseStepState the dropout sites read their per-step base from (None: arguments only, the round-5 behaviour).
-    The stream position is kept: switching modes moves it between ``offset`` and ``base``."""
+    The stream position is kept: switching modes moves it between ``offset`` and ``base``.  ``owner``: the object that keeps the
+    struct's memory alive (a stepstate.StepState); when it is collected the address is detached again, so no dropout site reads freed
+    memory.  Another state cannot be installed over a live one: detach it first (None)."""
+    address = None if not address else int(address)
+    if address is not None and _state["device_state"] not in (None, address):
+        raise RuntimeError("config.set_device_state: another device step state (0x%x) is installed; close its trainer first"
+                           % _state["device_state"])
     pos = _state["base"] + _state["offset"]
-    _state["device_state"] = None if not address else int(address)
+    if address != _state["device_state"] or owner is not None:
+        token = _state["device_token"] = object()
+        if owner is not None and address is not None:
+            weakref.finalize(owner, _release_device_state, token)
+    _state["device_state"] = address
     if _state["device_state"] is None:
         _state["offset"], _state["base"] = pos, 0
     else:
         _state["offset"], _state["base"] = 0, pos
+
+
+def _release_device_state(token):
+    if _state["device_token"] is token and _state["device_state"] is not None:
+        set_device_state(None)
 
 
 def device_state():

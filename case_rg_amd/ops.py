@@ -1683,6 +1683,8 @@ INTERACTION_FUSED = os.environ.get("CASE_INTERACTION_FUSED", "auto")
 def interaction_supported(Eq, Ep, needs_grad):
     if INTERACTION_FUSED == "off" or needs_grad or not (Eq.is_cuda and Eq.dtype == torch.bfloat16 and Ep.dtype == torch.bfloat16):
         return False
+    if Eq.shape[1] not in (1, Ep.shape[1]):
+        return False  # one query per sample, or one per passage: anything else is refused by the single launches
     if not A.lib.case_abi_features() & A.FEAT_INTERACTION:
         return False
     d = A.InteractionDesc()
@@ -1695,6 +1697,8 @@ def interaction_fwd(Eq, Ep, q_valid, p_valid, w):
     (G_p_q [B, P, Lq, 5H], G_q_p [B, P, Lp, 5H], A [B P, Lp, Lq], Bm^T [B P, Lq, Lp]).  No autograd."""
     B, nq, Lq, H = Eq.shape
     _, P, Lp, _ = Ep.shape
+    if nq not in (1, P):
+        raise ValueError("interaction_fwd: %d queries for %d passages (one query, or one per passage)" % (nq, P))
     n = B * P
     Eq, Ep = (t if t.is_contiguous() else t.contiguous() for t in (Eq.detach(), Ep.detach()))
     qv, pv = _u8(q_valid), _u8(p_valid)

@@ -82,6 +82,14 @@ class FusedAdam(torch.optim.Optimizer):
                     A.call("case_cast", p.data_ptr(), lp.data_ptr(), p.numel(), A.F32, ops._DT[lp.dtype], ops._stream())
                     ops.seed_param_cache(p, lp)
 
+    def seed_low_copies(self):
+        """Install the persistent operand copies as they stand (no cast: a replayed step's Adam kernel has just rewritten them)."""
+        for group in self.param_groups:
+            for p in group["params"]:
+                lp = self._low.get(id(p))
+                if lp is not None:
+                    ops.seed_param_cache(p, lp)
+
     def advance_host_steps(self, params):
         """A captured step was replayed: move the host-side step counts of the parameters it updates (state_dict / checkpoints)."""
         for p in params:
@@ -113,6 +121,10 @@ class FusedAdam(torch.optim.Optimizer):
         if ema is not None:
             names = {id(p): n for n, p in ema.model.named_parameters()}
             shadow_of = {pid: ema.shadow[n] for pid, n in names.items() if n in ema.shadow}
+        # ONE entry table over every group: the clip is global (``clip_grad_norm_(model.parameters(), 1)``, one norm over the union of
+        # the groups, taken before any group is updated), then one Adam launch per group over its own run of the chunk list
+        rows, runs, fresh, stepped = [], [], {}, []
+        dev = None
         for group in self.param_groups:
             # parameters with a gradient take the Adam update; those without one (unused this step: the reference builds DDP with
             # find_unused_parameters=True, and Masque alternates 'ps_train' / 'train') only have their EMA shadow moved, as
@@ -121,15 +133,17 @@ class FusedAdam(torch.optim.Optimizer):
             idle = [p for p in group["params"] if p.grad is None and p.requires_grad and id(p) in shadow_of]
             if not params and not idle:
                 continue  # (a group without any gradient still moves its EMA shadows: the idle entries below)
-            dev = (params or idle)[0].device
             if not (params or idle)[0].is_cuda:
                 raise RuntimeError("case_rg_amd.optim.FusedAdam runs on the GPU only; there is no CPU path")
+            if dev is None:
+                dev = (params or idle)[0].device
+            elif (params or idle)[0].device != dev:
+                raise RuntimeError("FusedAdam: every parameter group must live on one device")
             beta1, beta2 = group["betas"]
             lr = float(group["lr"])
-            entries = (_Entry * (len(params) + len(idle)))()
-            fresh = {}
+            first = len(rows)
             dev_state = state
-            for i, p in enumerate(params):
+            for p in params:
                 if p.dtype != torch.float32 or p.grad.dtype != torch.float32 or not p.is_contiguous():
                     raise TypeError("FusedAdam expects contiguous float32 parameters and gradients")
                 st = self.state[p]
@@ -153,56 +167,68 @@ class FusedAdam(torch.optim.Optimizer):
                     if lp is None or lp.shape != p.shape or lp.device != dev:
                         lp = self._low[id(p)] = torch.empty(p.shape, dtype=self.low_precision, device=dev)
                     fresh[id(p)] = lp
-                entries[i] = _Entry(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
-                                    0 if sh is None else sh.data_ptr(), 0 if lp is None else lp.data_ptr(), p.numel(),
-                                    lr / (1.0 - beta1 ** step), math.sqrt(1.0 - beta2 ** step))
+                rows.append((_Entry(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
+                                           0 if sh is None else sh.data_ptr(), 0 if lp is None else lp.data_ptr(), p.numel(),
+                                           lr / (1.0 - beta1 ** step), math.sqrt(1.0 - beta2 ** step)), p.numel()))
                 st["_g"] = g  # keep a non-contiguous gradient's copy alive until the launch has consumed it
-            for j, p in enumerate(idle):
-                entries[len(params) + j] = _Entry(p.data_ptr(), 0, 0, 0, shadow_of[id(p)].data_ptr(), 0, p.numel(), 0.0, 1.0)
-            raw = bytes(entries)
-            if capturing:
-                if self._table is None or self._table.numel() < len(raw) or self._table.device != dev or len(raw) > self._graph_stage.numel():
-                    raise RuntimeError("FusedAdam: run the step eagerly once before capturing it (the entry table is sized by the first step)")
-                # a memcpy node out of this capture's own pinned buffer: every replay re-uploads the captured table first
-                self._graph_stage[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-                self._table[:len(raw)].copy_(self._graph_stage[:len(raw)], non_blocking=True)
-            else:
-                if self._table is None or self._table.numel() < len(raw) or self._table.device != dev:
-                    self._table = torch.empty(max(len(raw), 4096), dtype=torch.uint8, device=dev)
-                    self._stage = [(torch.empty(self._table.numel(), dtype=torch.uint8).pin_memory(), None) for _ in range(3)]
-                stage, ev = self._stage[self._stage_next]
-                if ev is not None:
-                    ev.synchronize()  # its upload of three steps ago (long done: the host never runs three steps ahead of the device)
-                stage[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
-                self._table[:len(raw)].copy_(stage[:len(raw)], non_blocking=True)
-                ev = torch.cuda.Event()
-                ev.record()
-                self._stage[self._stage_next] = (stage, ev)
-                self._stage_next = (self._stage_next + 1) % len(self._stage)
-            table = self._table
-            chunks = self._chunk_list([p.numel() for p in params + idle], dev)
-            stream = torch.cuda.current_stream().cuda_stream
-            sumsq = None
-            if clip_norm is not None:
-                # [0] the squared global norm, [1:] one partial per chunk, summed in a fixed order by one workgroup: the clip
-                # coefficient is bit-identical on every data-parallel rank (and run to run)
-                if self._norm_ws is None or self._norm_ws.numel() != chunks.shape[0] + 1 or self._norm_ws.device != dev:
-                    self._norm_ws = torch.empty(chunks.shape[0] + 1, dtype=torch.float32, device=dev)
-                sumsq = self._norm_ws
-                A.call("case_optim_sumsq", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], sumsq.data_ptr() + 4, sumsq.data_ptr(),
-                       stream)
-            A.call("case_optim_adam_ema", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], None if sumsq is None else sumsq.data_ptr(),
-                   float(clip_norm or 0.0), beta1, beta2, group["eps"], 0.0 if ema is None else 1.0 - ema.decay,
-                   None if dev_state is None else dev_state.address, stream)
-            if capturing:  # (allocated outside the capture, read by its kernels on every replay)
-                self._graph_keep += [table, chunks, sumsq]
-            self.last_stepped += params
-            for p in params:
-                self.state[p].pop("_g", None)
-            # the kernel wrote the parameters behind autograd's back (_version did not move): drop every cached operand copy and
-            # seed the cache with the copies this pass produced
-            ops.invalidate_param_cache()
-            for p in params:
-                if id(p) in fresh:
-                    ops.seed_param_cache(p, fresh[id(p)])
+            for p in idle:
+                rows.append((_Entry(p.data_ptr(), 0, 0, 0, shadow_of[id(p)].data_ptr(), 0, p.numel(), 0.0, 1.0), p.numel()))
+            runs.append((first, len(rows), beta1, beta2, group["eps"], dev_state))
+            stepped += params
+        if not rows:
+            return loss
+        entries = (_Entry * len(rows))(*[e for e, _ in rows])
+        raw = bytes(entries)
+        if capturing:
+            if self._table is None or self._table.numel() < len(raw) or self._table.device != dev or len(raw) > self._graph_stage.numel():
+                raise RuntimeError("FusedAdam: run the step eagerly once before capturing it (the entry table is sized by the first step)")
+            # a memcpy node out of this capture's own pinned buffer: every replay re-uploads the captured table first
+            self._graph_stage[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            self._table[:len(raw)].copy_(self._graph_stage[:len(raw)], non_blocking=True)
+        else:
+            if self._table is None or self._table.numel() < len(raw) or self._table.device != dev:
+                self._table = torch.empty(max(len(raw), 4096), dtype=torch.uint8, device=dev)
+                self._stage = [(torch.empty(self._table.numel(), dtype=torch.uint8).pin_memory(), None) for _ in range(3)]
+            stage, ev = self._stage[self._stage_next]
+            if ev is not None:
+                ev.synchronize()  # its upload of three steps ago (long done: the host never runs three steps ahead of the device)
+            stage[:len(raw)].copy_(torch.frombuffer(bytearray(raw), dtype=torch.uint8))
+            self._table[:len(raw)].copy_(stage[:len(raw)], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            self._stage[self._stage_next] = (stage, ev)
+            self._stage_next = (self._stage_next + 1) % len(self._stage)
+        table = self._table
+        chunks = self._chunk_list([n for _, n in rows], dev)
+        # first chunk of every entry (the chunk list is entry-major): a group's chunks are the run between its first and its end entry
+        per = A.lib.case_optim_chunk_elems()
+        chunk_at = [0]
+        for _, n in rows:
+            chunk_at.append(chunk_at[-1] + (n + per - 1) // per)
+        stream = torch.cuda.current_stream().cuda_stream
+        sumsq = None
+        if clip_norm is not None:
+            # [0] the squared global norm, [1:] one partial per chunk, summed in a fixed order by one workgroup: the clip
+            # coefficient is bit-identical on every data-parallel rank (and run to run)
+            if self._norm_ws is None or self._norm_ws.numel() != chunks.shape[0] + 1 or self._norm_ws.device != dev:
+                self._norm_ws = torch.empty(chunks.shape[0] + 1, dtype=torch.float32, device=dev)
+            sumsq = self._norm_ws
+            A.call("case_optim_sumsq", table.data_ptr(), chunks.data_ptr(), chunks.shape[0], sumsq.data_ptr() + 4, sumsq.data_ptr(),
+                   stream)
+        for first, end, beta1, beta2, eps, dev_state in runs:
+            c0, c1 = chunk_at[first], chunk_at[end]
+            A.call("case_optim_adam_ema", table.data_ptr(), chunks.data_ptr() + c0 * chunks.stride(0) * chunks.element_size(), c1 - c0,
+                   None if sumsq is None else sumsq.data_ptr(), float(clip_norm or 0.0), beta1, beta2, eps,
+                   0.0 if ema is None else 1.0 - ema.decay, None if dev_state is None else dev_state.address, stream)
+        if capturing:  # (allocated outside the capture, read by its kernels on every replay)
+            self._graph_keep += [table, chunks, sumsq]
+        self.last_stepped = stepped
+        for p in stepped:
+            self.state[p].pop("_g", None)
+        # the kernel wrote the parameters behind autograd's back (_version did not move): drop every cached operand copy and
+        # seed the cache with the copies this pass produced
+        ops.invalidate_param_cache()
+        for p in stepped:
+            if id(p) in fresh:
+                ops.seed_param_cache(p, fresh[id(p)])
         return loss

@@ -54,6 +54,7 @@ class StepGraphs(object):
         self.graphs = {}
         self.disabled = set()
         self.replays = 0
+        self.low_epoch = -1  # ops.PARAM_EPOCH at which the optimizer's bf16 copies were last known to equal the parameters (a replay's end)
         # The reference's collate pads the answers of a batch to its LONGEST answer (CaSE/CaSEDataset.py:135-136), so data['response'] changes
         # shape from batch to batch while every other tensor is fixed-size: padded here with PAD (0) up to the model's max_target_length, all
         # batches share one captured step.  PAD targets are ignored by the loss (ignore_index 0, CaSE/Model.py:306), are masked as keys and sit
@@ -113,13 +114,16 @@ class StepGraphs(object):
             self.seen[sig] = 0
             return None
         if g.epoch != ops.PARAM_EPOCH:
-            # somebody rewrote parameters through .data since the last replay (EMA swap for evaluation, broadcast, eager steps of another
-            # shape): the captured forward reads the optimizer's persistent bf16 copies -- refresh them; moved storages end the capture
+            # somebody rewrote parameters through .data since the last replay of this graph (EMA swap for evaluation, broadcast, eager
+            # steps, another graph's replay): moved storages end the capture
             if g.pointers != self._pointers(optimizer):
                 del self.graphs[sig]
                 self.seen[sig] = 0
                 return None
-            optimizer.reseed_param_cache()
+            if self.low_epoch != ops.PARAM_EPOCH:
+                # the captured forward reads the optimizer's persistent bf16 copies: refresh them (not needed after a replay of another
+                # graph alone -- its Adam kernel rewrote them with the parameters)
+                optimizer.reseed_param_cache()
         for k, v in g.static.items():
             src = data[k]
             if src is not v:
@@ -141,7 +145,12 @@ class StepGraphs(object):
                 p.grad = None
         config.skip_rng(g.consumed)
         optimizer.advance_host_steps(g.stepped)
-        g.epoch = ops.PARAM_EPOCH
+        # the replay rewrote every parameter through raw pointers (_version did not move): drop every derived copy (chain packs, casts of
+        # views, folded decode projections, Highway packs) and reinstall the persistent bf16 copies the captured Adam kernel has just
+        # rewritten -- as they are, without a cast
+        ops.invalidate_param_cache()
+        optimizer.seed_low_copies()
+        g.epoch = self.low_epoch = ops.PARAM_EPOCH
         self.replays += 1
         if scheduler is not None:
             scheduler.step()

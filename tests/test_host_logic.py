@@ -327,3 +327,29 @@ def test_lr_schedule_equals_the_installed_transformers_implementation():
     for kw in ({}, {"num_cycles": 3}):
         a, b = trajectory(ref, **kw), trajectory(ours, **kw)
         assert max(abs(x - y) for x, y in zip(a, b)) <= 1e-12, kw
+
+
+def test_device_state_is_refused_over_another_and_leaves_with_its_owner():
+    import gc
+
+    class Owner(object):
+        pass
+
+    config.set_device_state(None)
+    owner = Owner()
+    config.set_device_state(0x7f0000002000, owner=owner)
+    config.set_device_state(0x7f0000002000)  # the same state again: a no-op
+    with pytest.raises(RuntimeError, match="another device step state"):
+        config.set_device_state(0x7f0000003000)
+    assert config.device_state() == 0x7f0000002000
+    del owner
+    gc.collect()
+    assert config.device_state() is None
+    stale = Owner()
+    config.set_device_state(0x7f0000002000, owner=stale)
+    config.set_device_state(None)
+    config.set_device_state(0x7f0000004000)
+    del stale
+    gc.collect()
+    assert config.device_state() == 0x7f0000004000, "a finalizer of an earlier state must not detach a later one"
+    config.set_device_state(None)

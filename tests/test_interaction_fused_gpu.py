@@ -209,3 +209,49 @@ def test_training_steps_do_not_keep_their_graphs_alive(bf16_mode):
         torch.cuda.synchronize()
         seen.append(torch.cuda.memory_allocated())
     assert seen[5] == seen[3] == seen[2], seen
+
+
+@pytest.mark.parametrize("grad", [False, True])
+def test_query_count_outside_one_or_p_is_refused(bf16_mode, grad):
+    """One query per sample or one per passage: nq = 2 against P = 4 raises as the single launches do (the reference's assertion,
+    common/Interaction.py:27) instead of indexing the queries as pair / P; nq = 1 and nq = P keep the fused launch."""
+    from case_rg_amd import _abi, ops
+    from case_rg_amd.common.Interaction import Interaction
+    B, P, Lp = 2, 4, 64
+    g = torch.Generator().manual_seed(17)
+    m = Interaction(H).to(DEV)
+    with torch.no_grad():
+        m.dual_att_linear.weight.copy_(torch.randn(1, 3 * H, generator=g).to(DEV) * 0.05)
+    Ep = (torch.randn(B, P, Lp, H, generator=g) * 0.7).to(DEV).to(torch.bfloat16).requires_grad_(grad)
+    pv = torch.ones(B, P, Lp, dtype=torch.bool, device=DEV)
+
+    def run(nq):
+        Eq = (torch.randn(B, nq, LQ, H, generator=g) * 0.7).to(DEV).to(torch.bfloat16).requires_grad_(grad)
+        qv = torch.ones(B, nq, LQ, dtype=torch.bool, device=DEV)
+        calls = {}
+        raw = _abi.call
+
+        def counting(name, *a):
+            calls[name] = calls.get(name, 0) + 1
+            return raw(name, *a)
+
+        _abi.call = counting
+        try:
+            with torch.set_grad_enabled(grad):
+                out = m(Eq, Ep, qv, pv)
+                if grad:
+                    (out[0].float().sum() + out[1].float().sum()).backward()
+        finally:
+            _abi.call = raw
+        return out, calls, Eq, qv
+
+    for nq in (1, P):
+        out, calls, _, _ = run(nq)
+        assert calls.get("case_interaction_fwd", 0) == 1, (nq, calls)
+        assert out[0].shape == (B, 1 if nq == 1 else P, LQ, 5 * H) and torch.isfinite(out[1].float()).all()
+    with pytest.raises(AssertionError):
+        run(2)
+    Eq = torch.zeros(B, 2, LQ, H, device=DEV, dtype=torch.bfloat16)
+    with pytest.raises(ValueError, match="2 queries for 4 passages"):
+        ops.interaction_fwd(Eq, Ep.detach(), torch.ones(B, 2, LQ, dtype=torch.bool, device=DEV), pv, m.dual_att_linear.weight)
+    assert not ops.interaction_supported(Eq, Ep, False)

@@ -166,3 +166,99 @@ def test_fused_adam_clip_is_bit_reproducible():
         assert all(torch.equal(a, b) for a, b in zip(ps, results[0][0]))
     want = sum(float((gr.double() ** 2).sum()) for gr in grads)
     assert abs(results[0][1] - want) <= 1e-5 * want
+
+
+def test_fused_adam_clips_every_group_by_one_global_norm():
+    """Two parameter groups (other learning rates, the same betas): the clip is ONE norm over the union of the groups, as
+    clip_grad_norm_(model.parameters(), 1) takes it -- not one norm per group.  Yardstick: torch.optim.Adam with the same groups,
+    clip_grad_norm_ and EMA.update, in float64 on copies."""
+    from case_rg_amd.common.EMA import EMA
+    from case_rg_amd.optim import FusedAdam
+    dev = torch.device("cuda", 0)
+    ma = _Holder(_params(dev, 11))
+    mb = _Holder([torch.nn.Parameter(p.detach().double().cpu()) for p in ma.parameters()])
+    ea, eb = EMA(ma, 0.995), EMA(mb, 0.995)
+    ea.register(), eb.register()
+
+    def groups(m):
+        ps = list(m.parameters())
+        return [{"params": ps[:3], "lr": 2e-3}, {"params": ps[3:], "lr": 5e-4}]
+
+    oa = FusedAdam(groups(ma), lr=1.0, low_precision=torch.bfloat16)
+    ob = torch.optim.Adam(groups(mb), lr=1.0)
+    g = torch.Generator().manual_seed(13)
+    for step in range(3):
+        scale = 10.0 if step == 1 else 0.01  # the global norm is above 1 in every step (about 4.5, then 4500): the clip binds
+        for pa, pb in zip(ma.parameters(), mb.parameters()):
+            gr = torch.randn(pa.shape, generator=g) * scale
+            pa.grad, pb.grad = gr.to(dev), gr.double()
+        oa.step(clip_norm=1.0, ema=ea)
+        norm = torch.nn.utils.clip_grad_norm_(mb.parameters(), 1.0)
+        ob.step()
+        eb.update()
+        assert step != 1 or norm > 10.0
+        for (n, pa), pb in zip(ma.named_parameters(), mb.parameters()):
+            sa, sb = oa.state[pa], ob.state[pb]
+            assert torch.allclose(sa["exp_avg"].double().cpu(), sb["exp_avg"], rtol=1e-5, atol=1e-9), (step, n)
+            assert torch.allclose(sa["exp_avg_sq"].double().cpu(), sb["exp_avg_sq"], rtol=1e-5, atol=1e-12), (step, n)
+            assert torch.allclose(pa.detach().double().cpu(), pb.detach(), rtol=1e-6, atol=1e-6), (step, n)
+            assert torch.allclose(ea.shadow[n].double().cpu(), eb.shadow[n], rtol=1e-6, atol=1e-6), (step, n)
+
+
+def test_captured_step_with_two_groups_replays_each_groups_own_entries():
+    """A captured optimizer step over two groups uploads ONE table that holds both groups' entries: every replay updates each group
+    from its own entries -- the same bits as the eager steps of a twin optimizer on the same gradients."""
+    from case_rg_amd.common.EMA import EMA
+    from case_rg_amd.optim import FusedAdam
+    from case_rg_amd.stepstate import StepState
+    dev = torch.device("cuda", 0)
+    ma, mb = _Holder(_params(dev, 8)), _Holder(_params(dev, 8))
+    ea, eb = EMA(ma, 0.99), EMA(mb, 0.99)
+    ea.register(), eb.register()
+
+    def groups(m):
+        ps = list(m.parameters())
+        return [{"params": ps[:3]}, {"params": ps[3:]}]
+
+    oa = FusedAdam(groups(ma), lr=1e-3, low_precision=torch.bfloat16)
+    ob = FusedAdam(groups(mb), lr=1e-3, low_precision=torch.bfloat16)
+    st = StepState(dev)
+    g = torch.Generator().manual_seed(9)
+    grads = [[torch.randn(p.shape, generator=g) * (10.0 if k == 2 else 0.05) for p in ma.parameters()] for k in range(4)]
+
+    def put(m, k):
+        for p, gr in zip(m.parameters(), grads[k]):
+            if p.grad is None:
+                p.grad = gr.to(dev)
+            else:
+                p.grad.copy_(gr.to(dev))  # in place: the captured step reads these addresses
+
+    put(ma, 0)
+    oa.stage_step(st)
+    st.upload(0)
+    oa.step(clip_norm=1.0, ema=ea, state=st)  # (sizes the entry table)
+    put(mb, 0)
+    ob.step(clip_norm=1.0, ema=eb)
+    oa.prepare_capture()
+    oa.stage_step(st)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        oa.step(clip_norm=1.0, ema=ea, state=st)
+    stepped = list(oa.last_stepped)
+    assert len(stepped) == len(list(ma.parameters()))
+    for p in stepped:  # the recording executed nothing
+        oa.state[p]["step"] = int(oa.state[p]["step"]) - 1
+    for k in range(1, 4):
+        put(ma, k)
+        oa.stage_step(st)
+        st.upload(0)
+        graph.replay()
+        oa.advance_host_steps(stepped)
+        put(mb, k)
+        ob.step(clip_norm=1.0, ema=eb)
+    torch.cuda.synchronize()
+    for (n, pa), pb in zip(ma.named_parameters(), mb.parameters()):
+        assert torch.equal(pa, pb), (n, (pa - pb).abs().max().item())
+        assert torch.equal(ea.shadow[n], eb.shadow[n]), n
+        assert torch.equal(oa.state[pa]["exp_avg_sq"], ob.state[pb]["exp_avg_sq"]) and oa.state[pa]["step"] == ob.state[pb]["step"] == 4

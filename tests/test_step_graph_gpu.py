@@ -323,3 +323,29 @@ def test_auto_capture_keeps_a_graph_only_where_it_pays(dropout_on, eager_ms, kep
     else:
         assert not trainer.graphs.graphs and trainer.graphs.replays == 3 and len(trainer.graphs.disabled) == 1
     trainer.close()
+
+
+def test_a_dropped_capturing_trainer_detaches_its_step_state(dropout_on):
+    """The process-wide dropout configuration holds the ADDRESS of a capturing trainer's step state.  A second capturing trainer cannot
+    take it over, and a trainer dropped without close() detaches it when its state is collected: the next dropout site draws the mask
+    of plain arguments instead of adding a base read from freed memory."""
+    import gc
+    from case_rg_amd import config, ops
+    x = torch.ones(256, 512, device=DEV, dtype=torch.bfloat16)
+    config.set_rng_state((4321, 1000))
+    want = ops.dropout(x, 0.5).clone()
+    trainer, opt, sched = _tiny_trainer(torch.bfloat16, capture=True)
+    assert config.device_state() == trainer.step_state.address
+    with pytest.raises(RuntimeError, match="another device step state"):
+        _tiny_trainer(torch.bfloat16, capture=True)
+    assert config.device_state() == trainer.step_state.address
+    trainer.train_batch(0, _batch(0), "train", opt, sched)
+    torch.cuda.synchronize()
+    del trainer, opt, sched
+    gc.collect()
+    assert config.device_state() is None
+    config.set_rng_state((4321, 1000))
+    assert torch.equal(ops.dropout(x, 0.5), want)
+    trainer, opt, sched = _tiny_trainer(torch.bfloat16, capture=True)  # the slot is free again
+    trainer.close()
+    assert config.device_state() is None
