@@ -10,7 +10,7 @@ Batch-first [N, L, E] inside; the sequence-first wrappers live in the layer modu
 import torch
 import torch.nn as nn
 
-from .. import config, ops
+from .. import config, ops, paramcache
 
 
 class _OutProj(nn.Module):
@@ -55,16 +55,14 @@ class MultiheadAttention(nn.Module):
 
     # -- K21: decode-time cross-attention on the raw memory (absorbed K / V projections) ------------
     def absorbed(self):
-        """The layer's projections folded for ops.attention_decode_mqa (inference; rebuilt when a parameter changes):
+        """The layer's projections folded for ops.attention_decode_mqa (inference; kept in paramcache until a parameter changes):
           wqk [heads E, E] bf16, bqk [heads E] f32:  qp_h = log2(e) / sqrt(d) Wk_h^T (Wq_h x + bq_h)   (q_h . bk_h is constant over the keys)
           wv  [E, E] bf16 (the V rows of in_proj_weight, head h = rows h d .. h d + d - 1: o_h = Wv_h c_h)
           bo  [E] f32 = out_proj.bias + out_proj.weight bv   (the probabilities of a row sum to one)"""
+        return paramcache.derived((self.in_proj_weight, self.in_proj_bias, self.out_proj.weight, self.out_proj.bias), "absorbed", self._fold)
+
+    def _fold(self):
         E, h, d = self.embed_dim, self.num_heads, self.head_dim
-        stamp = (ops.PARAM_EPOCH, self.in_proj_weight._version, self.in_proj_weight.data_ptr(), self.in_proj_bias._version,
-                 self.out_proj.weight._version, self.out_proj.bias._version, self.out_proj.weight.data_ptr())
-        hit = getattr(self, "_absorbed", None)
-        if hit is not None and hit[0] == stamp:
-            return hit[1]
         with torch.no_grad():
             w, b = self.in_proj_weight.detach(), self.in_proj_bias.detach()
             c = 1.4426950408889634 / (d ** 0.5)
@@ -74,10 +72,8 @@ class MultiheadAttention(nn.Module):
                      sc=(E * E, 0), alpha=c)
             bqk = (w[E:2 * E].reshape(h, d, E) * b[:E].reshape(h, d, 1)).sum(dim=1).mul_(c).reshape(h * E).contiguous()
             bo = (self.out_proj.bias.detach() + (self.out_proj.weight.detach() * b[2 * E:].reshape(1, E)).sum(dim=1)).contiguous()
-            pack = dict(wqk=ops.cast(wqk.reshape(h * E, E), torch.bfloat16), bqk=bqk.float(), bo=bo.float(),
+            return dict(wqk=ops.cast(wqk.reshape(h * E, E), torch.bfloat16), bqk=bqk.float(), bo=bo.float(),
                         wv=ops.cast_param(self.in_proj_weight[2 * E:], torch.bfloat16), wo=ops.cast_param(self.out_proj.weight, torch.bfloat16))
-        self._absorbed = (stamp, pack)
-        return pack
 
     def cross_attention_absorbed(self, x, memory, memory_valid=None, residual=None, ln_in=None):
         """x [N, 1, E] (one decode position per sequence), memory [N, S, E] RAW bf16 rows -> out_proj(attention) (+ residual).

@@ -7,13 +7,12 @@ stream.  There is no eager fallback: tensors must live on a ROCm device.
 import math
 import ctypes as C
 import os
-import weakref
 
 import torch
 from torch.autograd import Function
 
 from . import _abi as A
-from . import config
+from . import config, paramcache
 
 _DT = {torch.float32: A.F32, torch.bfloat16: A.BF16}
 
@@ -62,65 +61,33 @@ def _u8(mask):
 
 
 # ----------------------------------------------------------------------------------------------
-# parameter casting: fp32 master -> compute dtype, cached per (storage, version)
+# parameter casting: fp32 master -> compute dtype, kept in paramcache
 # ----------------------------------------------------------------------------------------------
-_cast_cache = {}
-
-
-PARAM_EPOCH = 0
-
-
 def invalidate_param_cache():
-    """Forget every cached low-precision parameter copy (and the fragment-ordered weight packs of the fused encoder chain).  ``_version`` does not move when a parameter is rewritten through
-    ``.data`` (``p.data = t``, ``p.data.copy_()``, ``xavier_uniform_(p.data)``, ``dist.broadcast(p.data)``), so the code paths
-    that do that -- ``EMA.apply_shadow`` / ``restore``, ``GradSync.broadcast_parameters``, ``init_params`` -- call this."""
-    _cast_cache.clear()
-    _chain_packs.clear()
-    global PARAM_EPOCH
-    PARAM_EPOCH += 1  # (modules that keep packed copies of their own parameters compare this counter: common/Highway.py)
-
-
-def seed_param_cache(p, low):
-    """Install ``low`` (a low-precision copy of the whole Parameter ``p`` made elsewhere, e.g. by the fused optimizer pass)."""
-    src = p.detach()
-    key = (id(p), src.storage_offset(), tuple(src.shape), tuple(src.stride()), low.dtype)
-    _cast_cache[key] = (weakref.ref(p), (p._version, p.data_ptr(), p.device), low)
-
-
-def _evict_dead():
-    for k in [k for k, v in _cast_cache.items() if v[0]() is None]:
-        del _cast_cache[k]
+    """Forget every copy derived from the parameters (paramcache.rewritten): the code paths that write through ``.data`` and so leave
+    ``_version`` where it was -- ``EMA.apply_shadow`` / ``restore``, ``GradSync.broadcast_parameters``, ``init_params`` -- call this."""
+    paramcache.rewritten()
 
 
 def cast_param(p, dtype):
-    """fp32 parameter -> operand of the compute dtype.  bf16 copies of nn.Parameters (and of views of them, e.g. the K/V rows
-    of ``in_proj_weight``) are cached until the parameter is updated in place (the optimizer step bumps ``_version``) or its
-    storage is swapped (``p.data = other`` changes ``data_ptr`` / device).  The cache is keyed by the owning Parameter object,
-    held through a weak reference: temporaries (``torch.cat`` of weights, test tensors) are never cached -- a freed tensor's
-    address can be handed to a new tensor of the same shape -- and entries of dead owners are dropped at the next miss."""
-    src = p.detach()
-    if src.dtype == dtype:
-        return src if src.is_contiguous() else src.contiguous()
+    """fp32 parameter -> operand of the compute dtype.  bf16 copies of nn.Parameters (and of views of them, e.g. the K/V rows of
+    ``in_proj_weight``) are kept in paramcache (the rule is there) under the owning Parameter and the view's geometry.  Temporaries
+    (``torch.cat`` of weights, test tensors) are never cached: a freed tensor's address can be handed to a new tensor of the same shape."""
+    if p.dtype == dtype:
+        return p.detach().contiguous()
     base = getattr(p, "_base", None)
     owner = p if isinstance(p, torch.nn.Parameter) else (base if isinstance(base, torch.nn.Parameter) else None)
     if owner is None:
-        return cast(src, dtype)
-    key = (id(owner), src.storage_offset(), tuple(src.shape), tuple(src.stride()), dtype)
-    stamp = (owner._version, owner.data_ptr(), owner.device)
-    hit = _cast_cache.get(key)
-    if hit is not None and hit[0]() is owner and hit[1] == stamp:
-        return hit[2]
-    if owner is not p and src.is_contiguous():  # a view (K/V rows of in_proj_weight ...): slice the whole-parameter copy if one is live
-        od = owner.detach()
-        whole = _cast_cache.get((id(owner), od.storage_offset(), tuple(od.shape), tuple(od.stride()), dtype))
-        if whole is not None and whole[0]() is owner and whole[1] == stamp and od.is_contiguous():
-            return whole[2].as_strided(src.shape, src.stride(), src.storage_offset() - od.storage_offset())
-    _evict_dead()
-    src = src.contiguous()
-    out = torch.empty(src.shape, dtype=dtype, device=src.device)
-    A.call("case_cast", _ptr(src), _ptr(out), src.numel(), _code(src), _DT[dtype], _stream())
-    _cast_cache[key] = (weakref.ref(owner), stamp, out)
-    return out
+        return cast(p.detach(), dtype)
+    owners, tag = (owner,), paramcache.cast_tag(p, dtype)
+    hit = paramcache.peek(owners, tag)
+    if hit is not None:
+        return hit
+    if owner is not p and p.is_contiguous() and owner.is_contiguous():  # a view (K/V rows of in_proj_weight ...): slice the whole-parameter copy if one is live
+        whole = paramcache.peek(owners, paramcache.cast_tag(owner, dtype))
+        if whole is not None:
+            return whole.as_strided(p.shape, p.stride(), p.storage_offset() - owner.storage_offset())
+    return paramcache.derived(owners, tag, lambda: cast(p.detach(), dtype))
 
 
 def cast(x, dtype):
@@ -138,7 +105,6 @@ def cast(x, dtype):
 # "auto": the chain runs wherever it is built (bf16, d_model = dim_feedforward = 512, no autograd, no dropout); "off": the
 # single-launch path (tests replay the same fixtures under both; A/B measurements)
 ENCODER_CHAIN = "auto"
-_chain_packs = {}
 
 
 def encoder_chain_supported(x, width, ffn_width, needs_grad):
@@ -147,18 +113,14 @@ def encoder_chain_supported(x, width, ffn_width, needs_grad):
 
 
 def _chain_pack(mats):
-    """Fragment-ordered bf16 pack of (Wo, W1, W2, Wqkv_next) -- any of them None -- cached until one of the parameters changes."""
-    key = tuple(0 if m is None else id(m) for m in mats)
-    stamp = tuple(None if m is None else (m._version, m.data_ptr()) for m in mats)
-    hit = _chain_packs.get(key)
-    if hit is not None and hit[0] == stamp and all((r is None) == (m is None) and (r is None or r() is m) for r, m in zip(hit[1], mats)):
-        return hit[2]
-    dev = next(m for m in mats if m is not None).device
-    low = [None if m is None else cast_param(m, torch.bfloat16) for m in mats]
-    packed = torch.empty(A.lib.case_encoder_chain_packed_bytes() // 2, dtype=torch.bfloat16, device=dev)
-    A.call("case_encoder_chain_pack", _ptr(low[0]), _ptr(low[1]), _ptr(low[2]), _ptr(low[3]), _ptr(packed), _stream())
-    _chain_packs[key] = (stamp, [None if m is None else weakref.ref(m) for m in mats], packed)
-    return packed
+    """Fragment-ordered bf16 pack of (Wo, W1, W2, Wqkv_next) -- any of them None -- kept in paramcache until one of the parameters changes."""
+    def build():
+        low = [None if m is None else cast_param(m, torch.bfloat16) for m in mats]
+        packed = torch.empty(A.lib.case_encoder_chain_packed_bytes() // 2, dtype=torch.bfloat16, device=next(m for m in mats if m is not None).device)
+        A.call("case_encoder_chain_pack", _ptr(low[0]), _ptr(low[1]), _ptr(low[2]), _ptr(low[3]), _ptr(packed), _stream())
+        return packed
+
+    return paramcache.derived(mats, "chain", build)
 
 
 def encoder_chain(variant, x_in, resid, layer, next_layer):
@@ -196,20 +158,9 @@ def encoder_chain(variant, x_in, resid, layer, next_layer):
 # Tiling of the GEMM calls issued from here: 0 = case_gemm's cost model, 128 / 256 = CaseGemmDesc.tile (tests and A/B
 # measurements run the same model under both tilings).  Host-side configuration: the library itself holds no state.
 GEMM_TILE = 0
-# Streams the package itself has put work on beside the caller's (common/heads.run_block_pair), by handle.  A backward pass then runs nodes -- and
-# their post-accumulate hooks -- on more than one stream: code that reads SEVERAL parameters' gradients from inside such a hook (parallel.GradSync)
-# calls join_aux_streams() first.
+# Streams the package itself has put work on beside the caller's (common/heads.run_block_pair), by handle.  A backward pass then runs post-accumulate
+# hooks on more than one stream: while this is non-empty, parallel.GradSync._on_grad records an event per gradient and the bucket's gather waits for those.
 AUX_STREAMS = {}
-
-
-def join_aux_streams():
-    """The current stream waits for everything queued so far on the other streams this package uses."""
-    if not AUX_STREAMS:
-        return
-    cur = torch.cuda.current_stream()
-    for handle, s in AUX_STREAMS.items():
-        if handle != cur.cuda_stream:
-            cur.wait_stream(s)
 
 
 # Measurement aid (bench.py): when a list, every launch appends the tile edge case_gemm_tile_for() reports for it.
@@ -342,7 +293,7 @@ class _ZeroArena:
     """Zero-initialised f32 memory for the gradients of one training step, handed out in slices of ONE fill: the backward pass asked
     for ~330 separately zeroed buffers per step (weight / bias gradients that are accumulated with atomics, LayerNorm and embedding
     gradients), each a 4-microsecond fill launch on a GPU-bound step.  The arena of a step is sized by what the previous step took
-    (steps are told apart by PARAM_EPOCH, which the optimizer bumps); the first step, and anything beyond the estimate, falls back to
+    (steps are told apart by paramcache.EPOCH); the first step, and anything beyond the estimate, falls back to
     one allocation per request.  Gradients are views of the arena: it is freed when the last of them dies (zero_grad, or GradSync's
     switch to its bucket views)."""
     ENABLED = os.environ.get("CASE_ZERO_ARENA", "1") != "0"
@@ -354,9 +305,9 @@ class _ZeroArena:
     def take(self, n, device):
         if not self.ENABLED or not torch.device(device).type == "cuda":
             return torch.zeros(n, dtype=torch.float32, device=device)
-        if self.epoch != PARAM_EPOCH or self.device != device:
+        if self.epoch != paramcache.EPOCH or self.device != device:
             self.want = self.served if self.device == device else 0
-            self.epoch, self.buf, self.pos, self.served, self.device = PARAM_EPOCH, None, 0, 0, device
+            self.epoch, self.buf, self.pos, self.served, self.device = paramcache.EPOCH, None, 0, 0, device
         step = (n + self.ALIGN - 1) // self.ALIGN * self.ALIGN
         self.served += step
         if self.buf is None or self.pos + step > self.buf.numel():

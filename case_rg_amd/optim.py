@@ -12,7 +12,7 @@ import math
 import torch
 
 from . import _abi as A
-from . import ops
+from . import ops, paramcache
 
 
 class _Entry(C.Structure):
@@ -71,24 +71,21 @@ class FusedAdam(torch.optim.Optimizer):
         n = max(4096, 0 if self._table is None else self._table.numel())
         self._graph_stage = torch.empty(n, dtype=torch.uint8).pin_memory()
         self._graph_keep.append(self._graph_stage)
-        ops.invalidate_param_cache()
-        self.reseed_param_cache()
+        self.refresh_low_copies()
+        paramcache.rewritten(keep=self.low_copies())
 
-    def reseed_param_cache(self):
+    def low_copies(self):
+        """(parameter, its persistent operand copy) of every parameter that has one."""
         for group in self.param_groups:
             for p in group["params"]:
-                lp = self._low.get(id(p))
-                if lp is not None:
-                    A.call("case_cast", p.data_ptr(), lp.data_ptr(), p.numel(), A.F32, ops._DT[lp.dtype], ops._stream())
-                    ops.seed_param_cache(p, lp)
+                if id(p) in self._low:
+                    yield p, self._low[id(p)]
 
-    def seed_low_copies(self):
-        """Install the persistent operand copies as they stand (no cast: a replayed step's Adam kernel has just rewritten them)."""
-        for group in self.param_groups:
-            for p in group["params"]:
-                lp = self._low.get(id(p))
-                if lp is not None:
-                    ops.seed_param_cache(p, lp)
+    def refresh_low_copies(self):
+        """Re-cast the parameters into the persistent operand copies and install those (nothing else is dropped: no rewrite event)."""
+        for p, lp in self.low_copies():
+            A.call("case_cast", p.data_ptr(), lp.data_ptr(), p.numel(), A.F32, ops._DT[lp.dtype], ops._stream())
+            paramcache.install((p,), paramcache.cast_tag(p, lp.dtype), lp)
 
     def advance_host_steps(self, params):
         """A captured step was replayed: move the host-side step counts of the parameters it updates (state_dict / checkpoints)."""
@@ -123,7 +120,7 @@ class FusedAdam(torch.optim.Optimizer):
             shadow_of = {pid: ema.shadow[n] for pid, n in names.items() if n in ema.shadow}
         # ONE entry table over every group: the clip is global (``clip_grad_norm_(model.parameters(), 1)``, one norm over the union of
         # the groups, taken before any group is updated), then one Adam launch per group over its own run of the chunk list
-        rows, runs, fresh, stepped = [], [], {}, []
+        rows, runs, fresh, stepped = [], [], [], []
         dev = None
         for group in self.param_groups:
             # parameters with a gradient take the Adam update; those without one (unused this step: the reference builds DDP with
@@ -166,7 +163,7 @@ class FusedAdam(torch.optim.Optimizer):
                     lp = self._low.get(id(p))
                     if lp is None or lp.shape != p.shape or lp.device != dev:
                         lp = self._low[id(p)] = torch.empty(p.shape, dtype=self.low_precision, device=dev)
-                    fresh[id(p)] = lp
+                    fresh.append((p, lp))
                 rows.append((_Entry(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                            0 if sh is None else sh.data_ptr(), 0 if lp is None else lp.data_ptr(), p.numel(),
                                            lr / (1.0 - beta1 ** step), math.sqrt(1.0 - beta2 ** step)), p.numel()))
@@ -225,10 +222,6 @@ class FusedAdam(torch.optim.Optimizer):
         self.last_stepped = stepped
         for p in stepped:
             self.state[p].pop("_g", None)
-        # the kernel wrote the parameters behind autograd's back (_version did not move): drop every cached operand copy and
-        # seed the cache with the copies this pass produced
-        ops.invalidate_param_cache()
-        for p in stepped:
-            if id(p) in fresh:
-                ops.seed_param_cache(p, fresh[id(p)])
+        # the kernel wrote the parameters behind autograd's back (_version did not move): every derived copy goes but the ones this pass produced
+        paramcache.rewritten(keep=fresh)
         return loss

@@ -23,7 +23,7 @@ import time
 
 import torch
 
-from . import config, ops
+from . import config, paramcache
 from .optim import FusedAdam
 
 
@@ -54,7 +54,7 @@ class StepGraphs(object):
         self.graphs = {}
         self.disabled = set()
         self.replays = 0
-        self.low_epoch = -1  # ops.PARAM_EPOCH at which the optimizer's bf16 copies were last known to equal the parameters (a replay's end)
+        self.low_epoch = -1  # paramcache.EPOCH at which the optimizer's bf16 copies were last known to equal the parameters (a replay's end)
         # The reference's collate pads the answers of a batch to its LONGEST answer (CaSE/CaSEDataset.py:135-136), so data['response'] changes
         # shape from batch to batch while every other tensor is fixed-size: padded here with PAD (0) up to the model's max_target_length, all
         # batches share one captured step.  PAD targets are ignored by the loss (ignore_index 0, CaSE/Model.py:306), are masked as keys and sit
@@ -113,17 +113,17 @@ class StepGraphs(object):
             del self.graphs[sig]  # moments / EMA shadows were replaced (load_state_dict, load_checkpoint): warm up and record again
             self.seen[sig] = 0
             return None
-        if g.epoch != ops.PARAM_EPOCH:
+        if g.epoch != paramcache.EPOCH:
             # somebody rewrote parameters through .data since the last replay of this graph (EMA swap for evaluation, broadcast, eager
             # steps, another graph's replay): moved storages end the capture
             if g.pointers != self._pointers(optimizer):
                 del self.graphs[sig]
                 self.seen[sig] = 0
                 return None
-            if self.low_epoch != ops.PARAM_EPOCH:
+            if self.low_epoch != paramcache.EPOCH:
                 # the captured forward reads the optimizer's persistent bf16 copies: refresh them (not needed after a replay of another
                 # graph alone -- its Adam kernel rewrote them with the parameters)
-                optimizer.reseed_param_cache()
+                optimizer.refresh_low_copies()
         for k, v in g.static.items():
             src = data[k]
             if src is not v:
@@ -145,12 +145,10 @@ class StepGraphs(object):
                 p.grad = None
         config.skip_rng(g.consumed)
         optimizer.advance_host_steps(g.stepped)
-        # the replay rewrote every parameter through raw pointers (_version did not move): drop every derived copy (chain packs, casts of
-        # views, folded decode projections, Highway packs) and reinstall the persistent bf16 copies the captured Adam kernel has just
-        # rewritten -- as they are, without a cast
-        ops.invalidate_param_cache()
-        optimizer.seed_low_copies()
-        g.epoch = self.low_epoch = ops.PARAM_EPOCH
+        # the replay rewrote every parameter through raw pointers (_version did not move): every derived copy goes but the persistent bf16
+        # copies, which the captured Adam kernel has just rewritten
+        paramcache.rewritten(keep=optimizer.low_copies())
+        g.epoch = self.low_epoch = paramcache.EPOCH
         self.replays += 1
         if scheduler is not None:
             scheduler.step()
@@ -230,7 +228,7 @@ class StepGraphs(object):
         for p in g.stepped:
             optimizer.state[p]["step"] = int(optimizer.state[p]["step"]) - 1
         config.skip_rng(-g.consumed)
-        g.epoch = ops.PARAM_EPOCH
+        g.epoch = paramcache.EPOCH
         g.opt_generation = optimizer.generation
         g.shadow = tr.ema.shadow
         g.pointers = self._pointers(optimizer)

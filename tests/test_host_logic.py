@@ -353,3 +353,112 @@ def test_device_state_is_refused_over_another_and_leaves_with_its_owner():
     gc.collect()
     assert config.device_state() == 0x7f0000004000, "a finalizer of an earlier state must not detach a later one"
     config.set_device_state(None)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# paramcache: the registry of weight-derived copies (CPU tensors; ``build`` callbacks that count their calls)
+# ---------------------------------------------------------------------------------------------------------------------------------
+class _Builds(object):
+    def __init__(self):
+        self.n = 0
+
+    def __call__(self):
+        self.n += 1
+        return torch.full((1,), float(self.n))
+
+
+@pytest.fixture()
+def registry():
+    from case_rg_amd import paramcache
+    paramcache.rewritten()
+    yield paramcache
+    paramcache.rewritten()
+
+
+def test_paramcache_serves_until_an_owner_moves(registry):
+    p, build = torch.nn.Parameter(torch.ones(3, 4)), _Builds()
+    first = registry.derived((p,), "x", build)
+    assert registry.derived((p,), "x", build) is first and build.n == 1 and registry.peek((p,), "x") is first
+    with torch.no_grad():
+        p.mul_(2.0)  # in place: _version moves
+    assert registry.peek((p,), "x") is None
+    second = registry.derived((p,), "x", build)
+    assert build.n == 2 and second is not first and registry.derived((p,), "x", build) is second
+    p.data = torch.zeros(3, 4)  # storage swap: data_ptr moves, _version does not
+    assert registry.peek((p,), "x") is None and registry.derived((p,), "x", build) is not second and build.n == 3
+    third = registry.peek((p,), "x")
+    p.data.mul_(3.0)  # silent: neither moves, so the registry has to be told
+    assert registry.derived((p,), "x", build) is third and build.n == 3
+    registry.rewritten()
+    assert registry.peek((p,), "x") is None and registry.derived((p,), "x", build) is not third and build.n == 4
+
+
+def test_paramcache_tracks_every_owner_and_keeps_none_in_place(registry):
+    a, b, c = (torch.nn.Parameter(torch.ones(2, 2)) for _ in range(3))
+    build = _Builds()
+    for n, mover in enumerate((a, b, c)):
+        value = registry.derived((a, b, c), "pack", build)
+        assert registry.derived((a, b, c), "pack", build) is value and build.n == n + 1
+        with torch.no_grad():
+            mover.add_(1.0)
+        assert registry.derived((a, b, c), "pack", build) is not value and build.n == n + 2, "one of several owners moved"
+    build = _Builds()
+    head, tail = registry.derived((None, a, b), "pack", build), registry.derived((a, b, None), "pack", build)
+    assert build.n == 2 and head is not tail
+    assert registry.derived((None, a, b), "pack", build) is head and registry.derived((a, b, None), "pack", build) is tail and build.n == 2
+    assert registry.peek((a, None, b), "pack") is None and registry.peek((a, b), "pack") is None
+    with torch.no_grad():
+        b.add_(1.0)
+    assert registry.peek((None, a, b), "pack") is None and registry.peek((a, b, None), "pack") is None
+
+
+def test_paramcache_tags_do_not_collide(registry):
+    p, one, two = torch.nn.Parameter(torch.ones(4, 4)), _Builds(), _Builds()
+    x, y = registry.derived((p,), "one", one), registry.derived((p,), ("two", 0), two)
+    assert x is not y and registry.derived((p,), "one", one) is x and registry.derived((p,), ("two", 0), two) is y
+    assert (one.n, two.n) == (1, 1) and registry.peek((p,), ("two", 1)) is None
+    assert [v for _, _, v in registry.entries("one")] == [x] and [v for _, _, v in registry.entries("two")] == [y]
+    assert len(list(registry.entries())) == 2
+
+
+def test_paramcache_forgets_dead_owners_and_is_not_fooled_by_a_recycled_id(registry):
+    import gc
+    build = _Builds()
+    data, keep = torch.ones(5), torch.nn.Parameter(torch.ones(2))
+    p = torch.nn.Parameter(data)
+    registry.derived((p,), "x", build)
+    registry.derived((keep, p), "y", build)
+    dead_id = id(p)
+    del p
+    gc.collect()
+    # new Parameters over the SAME storage (same data_ptr, _version 0, device) until one lands on the dead one's id(): only the weak
+    # reference tells them apart
+    held = []
+    while len(held) < 1000 and (not held or id(held[-1]) != dead_id):
+        held.append(torch.nn.Parameter(data))
+    assert id(held[-1]) == dead_id, "the interpreter did not hand the id() out again: nothing was tested"
+    assert any(None in owners for owners, _, _ in registry.entries("x"))  # dead, still listed: entries go at the next miss
+    assert registry.peek((held[-1],), "x") is None and registry.peek((keep, held[-1]), "y") is None
+    registry.derived((keep,), "z", build)
+    assert sorted(tag for _, tag, _ in registry.entries()) == ["z"]
+
+
+def test_paramcache_rewritten_keeps_the_optimizer_copies_where_cast_param_looks(registry):
+    params = [torch.nn.Parameter(torch.ones(6, 4)), torch.nn.Parameter(torch.ones(4))]
+    lows = [torch.zeros(6, 4, dtype=torch.bfloat16), torch.zeros(4, dtype=torch.bfloat16)]
+    other, build = torch.nn.Parameter(torch.ones(3)), _Builds()
+    registry.derived((other,), "chain", build)
+    registry.derived(tuple(params), "highway", build)
+    before = registry.EPOCH
+    registry.rewritten(keep=zip(params, lows))
+    assert registry.EPOCH == before + 1
+    left = list(registry.entries())
+    assert len(left) == 2 and {id(v) for _, _, v in left} == {id(t) for t in lows}
+    for p, low in zip(params, lows):
+        assert registry.peek((p,), registry.cast_tag(p, torch.bfloat16)) is low
+        assert registry.peek((p,), registry.cast_tag(p.detach(), torch.bfloat16)) is low  # cast_param builds the tag from the detached view
+    view = params[0][2:]  # a view of the first parameter: another geometry, another entry
+    assert registry.peek((params[0],), registry.cast_tag(view, torch.bfloat16)) is None
+    for n in range(3):
+        registry.rewritten()
+        assert registry.EPOCH == before + 2 + n and not list(registry.entries())

@@ -1125,7 +1125,7 @@ def test_fanout_sums_the_gradients_of_its_aliases_in_one_launch(dt):
 
 
 def test_zero_arena_serves_one_fill_per_step_with_disjoint_zeroed_slices():
-    """ops._ZeroArena: from the second step on (steps = optimizer updates = ops.PARAM_EPOCH) every zero-initialised gradient buffer of
+    """ops._ZeroArena: from the second step on (steps = parameter-rewrite events, paramcache.EPOCH) every zero-initialised gradient buffer of
     the backward pass is a slice of ONE zero-filled allocation sized by the previous step; slices are zero when handed out, disjoint,
     256-byte aligned, and requests beyond the estimate fall back to their own allocation."""
     ops = _ops()
@@ -1266,7 +1266,8 @@ def test_bf16_parameter_cache_follows_data_swaps_and_explicit_invalidation():
     gc.collect()
     live = torch.nn.Parameter(torch.zeros(4, 4, device=DEV))
     ops.cast_param(live, torch.bfloat16)  # a miss evicts the entries of dead owners
-    assert all(entry[0]() is not None for entry in ops._cast_cache.values())
+    from case_rg_amd import paramcache
+    assert all(o is not None for owners, _, _ in paramcache.entries("cast") for o in owners)
 
 
 def test_gemm_rejects_mismatched_aux_dtype():

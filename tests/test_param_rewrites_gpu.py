@@ -320,7 +320,7 @@ def test_replay_leaves_the_step_kernel_count_and_reinstalls_the_low_copies(bf16_
     """After a replay: no derived copy survives but the optimizer's bf16 copies, which are reinstalled as they are (no cast), and the
     next replay does not re-cast them either -- a replay gains no launch."""
     import case_rg_amd
-    from case_rg_amd import config, ops
+    from case_rg_amd import config, ops, paramcache
     trainer, opt = _case_trainer(hidden=64, lr=1e-3)
     try:
         for s in range(4):  # two eager steps, the recording step, one replay
@@ -333,11 +333,12 @@ def test_replay_leaves_the_step_kernel_count_and_reinstalls_the_low_copies(bf16_
         bias = next(p for p in trainer.model.parameters() if p.dim() == 1)
         ops.cast_param(bias, torch.bfloat16)  # a cached copy of a parameter the optimizer keeps no bf16 copy of
         low = {id(v) for v in opt._low.values()}
-        assert any(id(v[2]) not in low for v in ops._cast_cache.values())
+        assert any(id(v) not in low for _, _, v in paramcache.entries("cast"))
         trainer.train_batch(0, _batch(4, 64), "train", opt)
         low = {id(v) for v in opt._low.values()}
-        assert ops._cast_cache and all(id(v[2]) in low for v in ops._cast_cache.values()), "a derived copy survived the replay"
-        assert not ops._chain_packs
+        left = list(paramcache.entries())
+        assert left and all(id(v) in low for _, _, v in left), "a derived copy survived the replay"
+        assert not any(list(paramcache.entries(kind)) for kind in ("chain", "absorbed", "highway"))
         with _Counting() as c:
             trainer.train_batch(0, _batch(5, 64), "train", opt)
         assert trainer.graphs.replays == 4 and "case_cast" not in c.calls, c.calls
@@ -374,7 +375,7 @@ def _batch(step, Lp=64, device=DEV):
 
 def test_predict_between_replays_reads_the_replayed_weights(bf16_mode, monkeypatch):
     import case_rg_amd
-    from case_rg_amd import config, ops
+    from case_rg_amd import config, ops, paramcache
     monkeypatch.setattr(ops, "DECODE_ABSORB_MIN_KEYS", 16)  # K21 on these small memories (16 query rows, 2 x 64 passage rows)
     trainer, opt = _case_trainer(hidden=512, lr=1e-2)
     data = _batch(50, device=None)
@@ -396,23 +397,23 @@ def test_predict_between_replays_reads_the_replayed_weights(bf16_mode, monkeypat
         assert trainer.graphs.replays == 4
         second, _ = predict()
         # the derived copies the second predict read, against the same copies rebuilt from a cold cache
-        mhas = [m for m in trainer.model.modules() if hasattr(m, "_absorbed")]
-        warm_packs = {k: v[2].clone() for k, v in ops._chain_packs.items()}
-        warm_absorbed = [{k: v.clone() for k, v in m._absorbed[1].items()} for m in mhas]
+        by_owners = lambda kind: {tuple(map(id, owners)): v for owners, _, v in paramcache.entries(kind)}  # noqa: E731
+        warm_packs = {k: v.clone() for k, v in by_owners("chain").items()}
+        warm_folded = {k: {n: t.clone() for n, t in v.items()} for k, v in by_owners("absorbed").items()}
         ops.invalidate_param_cache()
         cold, _ = predict()
-        cold_packs = {k: v[2] for k, v in ops._chain_packs.items()}
-        cold_absorbed = [m._absorbed[1] for m in mhas]
+        cold_packs, cold_folded = by_owners("chain"), by_owners("absorbed")
     finally:
         trainer.close()
         config.set_device_state(None)
         case_rg_amd.set_dropout(False)
-    assert warm_packs and sorted(warm_packs) == sorted(cold_packs) and mhas
+    assert warm_packs and sorted(warm_packs) == sorted(cold_packs)
+    assert warm_folded and sorted(warm_folded) == sorted(cold_folded)
     for k, v in warm_packs.items():
         assert torch.equal(v, cold_packs[k]), "a chain pack outlived the replays"
-    for w, c in zip(warm_absorbed, cold_absorbed):
+    for owners, w in warm_folded.items():
         for k in w:
-            assert torch.equal(w[k], c[k]), "folded decode projection %s outlived the replays" % k
+            assert torch.equal(w[k], cold_folded[owners][k]), "folded decode projection %s outlived the replays" % k
     moved = _rel(second["rank"], first["rank"])
     assert moved >= 10 * COLD, "two replays barely moved the passage scores (%.3e)" % moved
     assert torch.equal(second["answer"], cold["answer"]), "predict after replays decoded other tokens than from a cold cache"

@@ -192,7 +192,8 @@ def test_gradsync_over_rccl_on_one_rank(ns, second_stream):
     """Drives the data-parallel machinery (post-accumulate hooks -> flat buckets -> asynchronous RCCL all-reduce ->
     scatter back) on a one-rank "nccl" group on the GPU: the synchronised gradients must equal the plain ones.
     ``second_stream``: with the query-side block stacks on their own stream (common/heads.run_block_pair; forced here, the policy reserves it for
-    GPU-bound geometries) the hooks fire on two streams -- GradSync joins them before it gathers a bucket (ops.join_aux_streams)."""
+    GPU-bound geometries) the hooks fire on two streams -- GradSync._on_grad records an event per gradient on the stream that produced it and
+    the bucket's gather waits for exactly those events."""
     import socket
     from case_rg_amd.common import heads
     keep_min = heads.SIDE_STREAM_MIN_ELEMS
