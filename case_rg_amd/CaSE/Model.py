@@ -57,7 +57,7 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
         return dec_out, gen, d1, d2
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
-                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None):
+                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None):
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
@@ -70,6 +70,9 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
             return dec_out, gen, (d1, d2), groundtruth_index
         if self.training:
             return None
+        if beam_width:
+            return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width,
+                              feature_of=lambda T: self._feature(additional_decoder_feature, T))
         return self._greedy(mems, valid, weights, source_map, BOS, max_target_length,
                             feature_of=lambda T: self._feature(additional_decoder_feature, T))
 
@@ -147,7 +150,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
-               span_extraction_result, output=None, max_target_length=None):
+               span_extraction_result, output=None, max_target_length=None, beam_width=None):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -162,7 +165,7 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep[0], passage_rep[0]], self.BOS, self.UNK, source_map,
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p])
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width)
 
 
 class CaSE(nn.Module):
@@ -183,6 +186,8 @@ class CaSE(nn.Module):
         self.id2vocab = id2vocab
         self.vocab_size = len(id2vocab)
         self.vocab2id = vocab2id
+        self.beam_width = 4  # do_beam's default width
+        self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
 
@@ -220,6 +225,17 @@ class CaSE(nn.Module):
 
     do_infer = do_test  # BASELINE.json's wording
 
+    def do_beam(self, data, width=None):
+        """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``: ``width`` hypotheses per
+        item ranked by length-normalised cost, retired on EOS): the ``do_test`` dict plus ``beam_score`` [B] (the answer's cum_cost / length),
+        ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer)."""
+        eq, ep, ps, se = self._encode_select_extract(data)
+        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                             encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
+                                             output=None, max_target_length=self.max_target_length,
+                                             beam_width=self.beam_width if width is None else width)
+        return {'answer': rg[3], 'rank': ps[0], 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
+
     def forward(self, data, method='mle_train'):
         # the reference expands data['source_map'] into a dense one-hot here (Utils.build_map, 15 GB at cfg 2);
         # the ids themselves feed the pointer scatter kernel instead
@@ -227,3 +243,5 @@ class CaSE(nn.Module):
             return self.do_train(data)
         elif method == 'test':
             return self.do_test(data)
+        elif method == 'beam':
+            return self.do_beam(data)

@@ -44,7 +44,7 @@ class MasqueTransformerSeqDecoder(PointerDecoderCore):
         return self._head(dec_in, x, ctxs, copies, None, source_map)
 
     def forward(self, encode_memories, BOS, UNK, source_map, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None):
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
@@ -57,6 +57,8 @@ class MasqueTransformerSeqDecoder(PointerDecoderCore):
             return dec_out, gen, dist, groundtruth_index
         if self.training:
             return None
+        if beam_width:
+            return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width)
         return self._greedy(mems, valid, weights, source_map, BOS, max_target_length)
 
 
@@ -103,7 +105,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query=None, encode_passage=None, passage_selection_result=None,
-               output=None, max_target_length=None):
+               output=None, max_target_length=None, beam_width=None):
         if encode_query is None:
             encode_query = self.query_encoder(query)[0][:, :, -1]
         if encode_passage is None:
@@ -117,7 +119,7 @@ class ResponseGeneration(nn.Module):
         prior_p = torch.sigmoid(passage_score).unsqueeze(-1).expand(-1, -1, passage_rep.size(2))
         return self.decoder([query_rep, passage_rep], self.BOS, self.UNK, source_map, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p])
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width)
 
 
 class Masque(nn.Module):
@@ -135,6 +137,8 @@ class Masque(nn.Module):
         self.id2vocab = id2vocab
         self.vocab_size = len(id2vocab)
         self.vocab2id = vocab2id
+        self.beam_width = 4  # do_beam's default width
+        self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
 
@@ -169,6 +173,16 @@ class Masque(nn.Module):
 
     do_infer = do_test
 
+    def do_beam(self, data, width=None):
+        """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``): the ``do_test`` dict
+        plus ``beam_score`` [B], ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (see CaSE.do_beam)."""
+        eq, ep, ps = self._encode_select(data)
+        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                             encode_passage=ep, passage_selection_result=ps, output=None,
+                                             max_target_length=self.max_target_length,
+                                             beam_width=self.beam_width if width is None else width)
+        return {'answer': rg[3], 'rank': ps[0], 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
+
     def forward(self, data, method='mle_train'):
         if method == 'train':
             return self.do_train(data)
@@ -176,3 +190,5 @@ class Masque(nn.Module):
             return self.do_ps_train(data)
         elif method == 'test':
             return self.do_test(data)
+        elif method == 'beam':
+            return self.do_beam(data)

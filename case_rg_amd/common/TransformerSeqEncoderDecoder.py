@@ -110,6 +110,9 @@ class PointerDecoderCore(nn.Module):
         self.eos_id = None
         self.eos_check_every = 8
         self.last_greedy_steps = 0
+        self.last_beam_steps = 0
+        # beam search retires a hypothesis on this id (the task models set it to EOS); None: every hypothesis runs to max_target_length
+        self.beam_eos_id = None
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, encode_memories, encode_masks, encode_weights, batch_size):
@@ -155,12 +158,9 @@ class PointerDecoderCore(nn.Module):
             copies.append(p)
         return dec_in, x, ctxs, copies
 
-    def _greedy(self, mems, valid, weights, source_map, BOS, max_target_length, feature_of=None):
-        """KV-cached greedy decoding (K13).  Step semantics are the reference's (CaSE/Model.py:94-123): fixed number of steps,
-        argmax of the newest position with the lowest index on ties, PAD tokens in the prefix masked as keys -- but each step
-        computes ONE new position: self-attention K/V of earlier positions, the per-layer K/V projections of both memories and
-        the additive-attention keys are cached, so a step streams the caches once instead of recomputing the prefix
-        (O(T) instead of O(T^2) decoder work, no per-step projection of the 3840-token passage memory)."""
+    def _cache_setup(self, mems, max_target_length, feat):
+        """What a cached decoding pass (greedy or beam) builds once: the step-invariant memory projections, one empty self-attention cache
+        per layer, the prefix validity and the step-invariant halves of the additive-attention queries."""
         B, dev = mems[0].shape[0], mems[0].device
         # the raw-pointer decode kernels (K21 / K22 / K23) have no autograd Function behind them: eval mode AND no_grad (the reference only
         # predicts under no_grad; a caller that differentiates an eval-mode greedy pass keeps the differentiable launches)
@@ -168,37 +168,52 @@ class PointerDecoderCore(nn.Module):
         cache = self._memory_cache(mems, absorb=inference)
         self_kvs = [dec.new_self_cache(B, max_target_length, mems[0]) for dec in self.decs]
         hist_valid = torch.zeros(B, max_target_length, dtype=torch.bool, device=dev)
-        table, pos = self.embedding[0].weight, self.embedding[1]
-        if max_target_length > pos.pe.size(0):
-            raise RuntimeError("max_target_length %d exceeds max_len %d" % (max_target_length, pos.pe.size(0)))
-        ids = self._bos(B, BOS, dev)
-        feat = None if feature_of is None else feature_of(1)
+        if max_target_length > self.embedding[1].pe.size(0):
+            raise RuntimeError("max_target_length %d exceeds max_len %d" % (max_target_length, self.embedding[1].pe.size(0)))
         # the feature half of the additive-attention query does not change over the steps: projected once per pass (BilinearAttention.split_query)
         splits = [self.attns[i].split_query(feat, self.hidden_size) if (QUERY_SPLIT and inference and feat is not None and cache[i]["eu"] is not None) else None
                   for i in range(len(mems))]
+        return inference, cache, self_kvs, hist_valid, splits
+
+    def _cached_layers(self, t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid):
+        """Position ``t`` of every row through the decoder stacks and the additive attentions, against the caches: (dec_in, x, ctxs, copies)."""
+        table, pos = self.embedding[0].weight, self.embedding[1]
+        tok_valid = ids.ne(0)
+        hist_valid[:, t] = tok_valid[:, 0]
+        dec_in = ops.embed_pos(ids, table, pos.pe[t:t + 1])  # position t
+        x = dec_in
+        ctxs, copies = [], []
+        for i, mem in enumerate(mems):
+            x = self.decs[i].step(x, t, self_kvs[i], hist_valid, cache[i]["kvs"], valid[i])
+            q = x if (feat is None or splits[i] is not None) else torch.cat([x, feat], dim=-1)
+            if cache[i]["eu"] is not None:  # K22: scores, softmax, prior renormalisation and context in one launch
+                ctx, p = self.attns[i].attend_decode(q, mem, tok_valid, valid[i], cache[i]["eu"], None if weights is None else weights[i],
+                                                     split=splits[i])
+            else:
+                ctx, p = self.attns[i].attend(q, mem, mem, row_valid=tok_valid, col_valid=valid[i], uh=cache[i]["uh"])
+                if weights is not None:
+                    p = weights[i].unsqueeze(1) * p
+                    p = p / (1e-8 + p.sum(dim=-1, keepdim=True))
+            ctxs.append(ctx)
+            copies.append(p)
+        return dec_in, x, ctxs, copies
+
+    def _greedy(self, mems, valid, weights, source_map, BOS, max_target_length, feature_of=None):
+        """KV-cached greedy decoding (K13).  Step semantics are the reference's (CaSE/Model.py:94-123): fixed number of steps,
+        argmax of the newest position with the lowest index on ties, PAD tokens in the prefix masked as keys -- but each step
+        computes ONE new position: self-attention K/V of earlier positions, the per-layer K/V projections of both memories and
+        the additive-attention keys are cached, so a step streams the caches once instead of recomputing the prefix
+        (O(T) instead of O(T^2) decoder work, no per-step projection of the 3840-token passage memory)."""
+        B, dev = mems[0].shape[0], mems[0].device
+        feat = None if feature_of is None else feature_of(1)
+        inference, cache, self_kvs, hist_valid, splits = self._cache_setup(mems, max_target_length, feat)
+        ids = self._bos(B, BOS, dev)
         picked = []
         finished = None if self.eos_id is None else torch.zeros(B, dtype=torch.bool, device=dev)
         capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
         fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, self.tgt_vocab_size, len(mems)))
         for t in range(max_target_length):
-            tok_valid = ids.ne(0)
-            hist_valid[:, t] = tok_valid[:, 0]
-            dec_in = ops.embed_pos(ids, table, pos.pe[t:t + 1])  # position t
-            x = dec_in
-            ctxs, copies = [], []
-            for i, mem in enumerate(mems):
-                x = self.decs[i].step(x, t, self_kvs[i], hist_valid, cache[i]["kvs"], valid[i])
-                q = x if (feat is None or splits[i] is not None) else torch.cat([x, feat], dim=-1)
-                if cache[i]["eu"] is not None:  # K22: scores, softmax, prior renormalisation and context in one launch
-                    ctx, p = self.attns[i].attend_decode(q, mem, tok_valid, valid[i], cache[i]["eu"], None if weights is None else weights[i],
-                                                         split=splits[i])
-                else:
-                    ctx, p = self.attns[i].attend(q, mem, mem, row_valid=tok_valid, col_valid=valid[i], uh=cache[i]["uh"])
-                    if weights is not None:
-                        p = weights[i].unsqueeze(1) * p
-                        p = p / (1e-8 + p.sum(dim=-1, keepdim=True))
-                ctxs.append(ctx)
-                copies.append(p)
+            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid)
             if fused_head:  # K23: vocabulary softmax, mixing, pointer scatter and argmax in one launch
                 dec_out, gen_in = self._head_parts(dec_in, x, feat)
                 # the distributions leave the device for the LAST step only (what the caller gets back); with an EOS-aware early stop any
@@ -221,9 +236,57 @@ class PointerDecoderCore(nn.Module):
             answer = torch.nn.functional.pad(answer, (0, max_target_length - answer.size(1)))
         return dec_out, gen, dist, answer
 
-    def _head_decode(self, dec_out, gen_in, ctxs, copies, source_map, want_dists=True):
-        """The head of one greedy step through K23 (ops.pointer_head_decode): the two generator Linears and the mixing Linear, then ONE
-        launch for softmax over V, softmax over the mixing logits, p0 x gen + the pointer scatter, and the argmax."""
+    def _beam(self, mems, valid, weights, source_map, BOS, max_target_length, width, feature_of=None):
+        """Beam search over the cached step (the reference's common/Generations.py:112-190, per item on the device).  The slots of an item
+        are extra batch rows (row b * W + w): memories, masks, copy priors, the e^{2 uh} caches and the sorted source keys are repeated W
+        times once per pass, and every step is ``_greedy``'s step on B * W rows followed by K24 (top-W of the mixed distribution), K25
+        (the per-item merge, EOS / last-step retirement), K26 (the self-attention caches reordered by the chosen parents into a second
+        set of buffers) and, after the last step, K27 (the back-track).  A hypothesis retires on ``beam_eos_id`` or at ``max_target_length``.
+        -> (dec_out of the last step's rows, None, None, answer [B, T], beam_answers [B, W, T], beam_scores [B, W])."""
+        B, dev, W, T = mems[0].shape[0], mems[0].device, int(width), max_target_length
+        if not ops.beam_supported(W):
+            raise RuntimeError("beam search: width %d is outside what the beam kernels are built for (1 .. 8)" % W)
+        mems = [m.repeat_interleave(W, dim=0) for m in mems]
+        valid = [v.repeat_interleave(W, dim=0) for v in valid]
+        weights = None if weights is None else [w.repeat_interleave(W, dim=0) for w in weights]
+        if isinstance(source_map, ops.SortedSource):
+            source_map = source_map.expand(W)
+        else:
+            source_map = source_map.repeat_interleave(W, dim=0)
+        feat = None if feature_of is None else feature_of(1).repeat_interleave(W, dim=0)
+        inference, cache, kv_a, valid_a, splits = self._cache_setup(mems, T, feat)
+        kv_b = [[torch.zeros_like(c) for c in layers] for layers in kv_a]  # K26's destination: the two sets swap roles every step
+        valid_b = torch.zeros_like(valid_a)
+        flat_a, flat_b = [c for layers in kv_a for c in layers], [c for layers in kv_b for c in layers]
+        state = ops.BeamState(B, W, T, dev)
+        ids = self._bos(B * W, BOS, dev)
+        capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
+        fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, self.tgt_vocab_size, len(mems)))
+        steps = 0
+        for t in range(T):
+            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, kv_a, valid_a)
+            if fused_head:  # K24: vocabulary softmax, mixing, pointer scatter and the W best entries in one launch
+                dec_out, gen_in = self._head_parts(dec_in, x, feat)
+                logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
+                _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, [c.reshape(B * W, -1) for c in copies], W)
+            else:  # no K23 for this pass (or a differentiated one): the unfused distribution and torch.topk feed the same beam kernels
+                dec_out, _, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
+                cand_p, cand_id = torch.topk(dist[:, -1].detach().float(), W, dim=-1)
+            ops.beam_advance(state, cand_p, cand_id, t, self.beam_eos_id)
+            ids = state.token.view(B * W, 1)
+            steps = t + 1
+            if steps == T:
+                break
+            ops.beam_gather(flat_a, flat_b, state.parent, t, valid_a, valid_b)
+            kv_a, kv_b, flat_a, flat_b, valid_a, valid_b = kv_b, kv_a, flat_b, flat_a, valid_b, valid_a
+            if not capturing and steps % self.eos_check_every == 0 and not bool(state.alive.any()):
+                break
+        self.last_beam_steps = steps
+        answer, beam_answers, beam_scores = ops.beam_backtrack(state)
+        return dec_out, None, None, answer, beam_answers, beam_scores
+
+    def _head_logits(self, dec_out, gen_in, ctxs):
+        """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 take."""
         B, V = dec_out.shape[0], self.tgt_vocab_size
         h = ops.linear(gen_in, self.gen[0].weight, self.gen[0].bias)
         logits = ops.linear(h, self.gen[-2].weight, None, out_dtype=torch.float32)
@@ -232,7 +295,14 @@ class PointerDecoderCore(nn.Module):
             mix_logits = ops.linear_skinny(parts, self.mix.weight, self.mix.bias)
         else:
             mix_logits = ops.linear(torch.cat(parts, dim=-1), self.mix.weight, self.mix.bias, out_dtype=torch.float32)
-        gen, dist, ids = ops.pointer_head_decode(logits.reshape(B, V), mix_logits.reshape(B, -1), source_map, [c.reshape(B, -1) for c in copies],
+        return logits.reshape(B, V), mix_logits.reshape(B, -1)
+
+    def _head_decode(self, dec_out, gen_in, ctxs, copies, source_map, want_dists=True):
+        """The head of one greedy step through K23 (ops.pointer_head_decode): the two generator Linears and the mixing Linear, then ONE
+        launch for softmax over V, softmax over the mixing logits, p0 x gen + the pointer scatter, and the argmax."""
+        B, V = dec_out.shape[0], self.tgt_vocab_size
+        logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
+        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, [c.reshape(B, -1) for c in copies],
                                                  want_gen=want_dists, want_dist=want_dists)
         if not want_dists:
             return None, None, ids.unsqueeze(1)
@@ -296,7 +366,7 @@ class TransformerSeqDecoder(PointerDecoderCore):
         return torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None):
         source_map = self._source(source_maps) if isinstance(source_maps, (list, tuple)) else source_maps
         B = source_map.size(0)
         source_map = self._sorted(source_map)
@@ -310,4 +380,6 @@ class TransformerSeqDecoder(PointerDecoderCore):
             return dec_out, gen, dist, groundtruth_index
         if self.training:
             return None
+        if beam_width:
+            return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width)
         return self._greedy(mems, valid, weights, source_map, BOS, max_target_length)

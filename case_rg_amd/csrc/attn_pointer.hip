@@ -478,15 +478,10 @@ struct HeadArgs {
   int nmem;
 };
 
-__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a) {
-  extern __shared__ __attribute__((aligned(16))) float ph_smem[];
-  float* row = ph_smem;                                  // [V]
-  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
-  float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);                       // [PH_THREADS]
-  float* red = tv + PH_THREADS;                                                    // [64] reduction scratch
-  __shared__ int64_t best_i[16];
-  __shared__ float best_v[16];
-  const int64_t b = blockIdx.x, V = a.V;
+// the row build shared by K23 and its beam form: row[0 .. V) = pm_0 softmax(logits) + the pointer mass of the sorted source keys (gen written
+// on the way when asked for).  Ends behind a barrier: every thread may read the whole row.
+__device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float* row, uint32_t* tk, float* tv, float* red, const int64_t b) {
+  const int64_t V = a.V;
   const int tid = threadIdx.x;
   // the mixing probabilities (1 + nmem <= 5 values; every thread computes them)
   float pm[1 + PH_MAX_MEM];
@@ -562,6 +557,19 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
     }
     __syncthreads();
   }
+}
+
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a) {
+  extern __shared__ __attribute__((aligned(16))) float ph_smem[];
+  float* row = ph_smem;                                  // [V]
+  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
+  float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);                       // [PH_THREADS]
+  float* red = tv + PH_THREADS;                                                    // [64] reduction scratch
+  __shared__ int64_t best_i[16];
+  __shared__ float best_v[16];
+  const int64_t b = blockIdx.x, V = a.V;
+  const int tid = threadIdx.x;
+  pointer_head_build_row(a, row, tk, tv, red, b);
   // outputs: the distribution row and its argmax (lowest index on ties)
   float bv = -INFINITY;
   int64_t bi = V;
@@ -595,6 +603,70 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
       }
     a.ids[b] = bi < V ? bi : 0;
     if (a.top) a.top[b] = bv;
+  }
+}
+
+// ---- K24: the beam step's head = K23 with a top-W tail ---------------------------------------------------------------------------
+// The same row build; instead of one argmax, W rounds of the block argmax over the LDS row, round r restricted to the entries that come
+// strictly after round r-1's winner in the order (probability descending, id ascending).  That order is total, so the W winners are the
+// W largest entries with the lowest id first on ties, whatever the scheduling; round 0 is K23's argmax comparison for comparison, so W = 1
+// returns K23's id and value bit for bit.  Scratch on top of K23's: two words for the previous winner.
+constexpr int PH_MAX_W = 8;
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const HeadArgs a, float* __restrict__ cand_p, int64_t* __restrict__ cand_id,
+                                                                       const int W) {
+  extern __shared__ __attribute__((aligned(16))) float ph_smem[];
+  float* row = ph_smem;
+  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
+  float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);
+  float* red = tv + PH_THREADS;
+  __shared__ int64_t best_i[16];
+  __shared__ float best_v[16];
+  __shared__ int64_t win_i;
+  __shared__ float win_v;
+  const int64_t b = blockIdx.x, V = a.V;
+  const int tid = threadIdx.x;
+  pointer_head_build_row(a, row, tk, tv, red, b);
+  float pv = INFINITY;  // the previous round's winner: round 0 admits every entry
+  int64_t pi = -1;
+  for (int r = 0; r < W; ++r) {
+    float bv = -INFINITY;
+    int64_t bi = V;
+    for (int64_t i = tid; i < V; i += PH_THREADS) {
+      const float x = row[i];
+      if (r == 0 && a.dist) a.dist[b * V + i] = x;
+      if (x > bv && (x < pv || (x == pv && i > pi))) {  // indices ascend within a thread: the first maximum is kept
+        bv = x;
+        bi = i;
+      }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      const float ov = __shfl_xor(bv, o, 64);
+      const int64_t oi = __shfl_xor(bi, o, 64);
+      if (ov > bv || (ov == bv && oi < bi)) {
+        bv = ov;
+        bi = oi;
+      }
+    }
+    if ((tid & 63) == 0) {
+      best_v[tid >> 6] = bv;
+      best_i[tid >> 6] = bi;
+    }
+    __syncthreads();
+    if (tid == 0) {
+      for (int w = 1; w < PH_THREADS / 64; ++w)
+        if (best_v[w] > bv || (best_v[w] == bv && best_i[w] < bi)) {
+          bv = best_v[w];
+          bi = best_i[w];
+        }
+      cand_id[b * W + r] = bi < V ? bi : 0;
+      cand_p[b * W + r] = bv;
+      win_v = bv;
+      win_i = bi;
+    }
+    __syncthreads();
+    pv = win_v;
+    pi = win_i;
   }
 }
 
@@ -836,15 +908,12 @@ extern "C" int case_pointer_attend_decode(const float* wq, const float* wq_add, 
   return case_check_launch("case_pointer_attend_decode");
 }
 
-extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
-                                        int64_t S, case_stream_t stream) {
-  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && ids && B > 0 && V > 0 && S > 0 && nmem >= 1 && B < (1ll << 31),
-               "case_pointer_head_decode: bad argument");
+static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
+                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S) {
+  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && B > 0 && V > 0 && S > 0 && nmem >= 1 && B < (1ll << 31), "%s: bad argument", who);
   if (nmem > PH_MAX_MEM || V > 36000 || S > 32768)
-    return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_decode: built for <= %d memories, V <= 36000, S <= 32768 (run the softmax / "
-                                              "scatter / argmax launches)", PH_MAX_MEM);
-  HeadArgs a;
+    return case_set_error(CASE_E_UNSUPPORTED, "%s: built for <= %d memories, V <= 36000, S <= 32768 (run the softmax / "
+                                              "scatter / argmax launches)", who, PH_MAX_MEM);
   a.logits = logits;
   a.mix_logits = mix_logits;
   a.keys = keys;
@@ -853,17 +922,30 @@ extern "C" int case_pointer_head_decode(const float* logits, const float* mix_lo
     a.copy[m] = m < nmem ? copies[m] : nullptr;
     a.len[m] = m < nmem ? lens[m] : 0;
     total += a.len[m];
-    CASE_REQUIRE(m >= nmem || (copies[m] && lens[m] > 0), "case_pointer_head_decode: null copy weights");
+    CASE_REQUIRE(m >= nmem || (copies[m] && lens[m] > 0), "%s: null copy weights", who);
   }
-  CASE_REQUIRE(total == S, "case_pointer_head_decode: the memories hold %lld positions, the source map %lld", (long long)total, (long long)S);
+  CASE_REQUIRE(total == S, "%s: the memories hold %lld positions, the source map %lld", who, (long long)total, (long long)S);
   a.gen = gen;
   a.dist = dist;
-  a.ids = ids;
-  a.top = top;
+  a.ids = nullptr;
+  a.top = nullptr;
   a.V = V;
   a.S = S;
   a.nmem = nmem;
-  const size_t lds = (size_t)(((V + 3) & ~(int64_t)3) + (PH_THREADS + 4) + PH_THREADS + 64) * 4;
+  return CASE_OK;
+}
+
+static size_t pointer_head_lds(int64_t V) { return (size_t)(((V + 3) & ~(int64_t)3) + (PH_THREADS + 4) + PH_THREADS + 64) * 4; }
+
+extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                        int64_t S, case_stream_t stream) {
+  CASE_REQUIRE(ids, "case_pointer_head_decode: bad argument");
+  HeadArgs a;
+  const int rc = pointer_head_args(a, "case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
+  if (rc != CASE_OK) return rc;
+  a.ids = ids;
+  a.top = top;
   static bool attr = false;
   if (!attr) {
     if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
@@ -871,8 +953,27 @@ extern "C" int case_pointer_head_decode(const float* logits, const float* mix_lo
       return case_set_error(CASE_E_LAUNCH, "case_pointer_head_decode: cannot reserve LDS");
     attr = true;
   }
-  hipLaunchKernelGGL(pointer_head_decode_kernel, dim3((unsigned)B), dim3(PH_THREADS), lds, (hipStream_t)stream, a);
+  hipLaunchKernelGGL(pointer_head_decode_kernel, dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a);
   return case_check_launch("case_pointer_head_decode");
+}
+
+extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                      int64_t V, int64_t S, int32_t W, case_stream_t stream) {
+  CASE_REQUIRE(cand_p && cand_id, "case_pointer_head_beam: bad argument");
+  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_beam: width %d outside 1 .. min(%d, V)", W, PH_MAX_W);
+  HeadArgs a;
+  const int rc = pointer_head_args(a, "case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+  if (rc != CASE_OK) return rc;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
+        hipSuccess)
+      return case_set_error(CASE_E_LAUNCH, "case_pointer_head_beam: cannot reserve LDS");
+    attr = true;
+  }
+  hipLaunchKernelGGL(pointer_head_beam_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id, (int)W);
+  return case_check_launch("case_pointer_head_beam");
 }
 
 extern "C" int case_copy_scatter_fwd(const int64_t* src, const float* w, float* dist, int64_t B, int64_t T, int64_t S,

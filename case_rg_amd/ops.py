@@ -1951,6 +1951,91 @@ def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, w
     return gen, dist, ids
 
 
+def beam_supported(width):
+    return 1 <= width <= 8 and bool(A.lib.case_abi_features() & A.FEAT_BEAM_DECODE)
+
+
+def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False):
+    """K24, ``pointer_head_decode`` with a top-``width`` tail: -> (gen [R, V] | None, dist [R, V] | None, cand_p f32 [R, W], cand_id int64 [R, W]),
+    the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference)."""
+    R, V = logits.shape
+    logits = logits if logits.is_contiguous() else logits.contiguous()
+    mix_logits = mix_logits.float().contiguous()
+    cs = [c.float().contiguous() for c in copies]
+    n = len(cs)
+    ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
+    lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
+    gen = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_gen else None
+    dist = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_dist else None
+    cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
+    cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
+    A.call("case_pointer_head_beam", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
+           _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, source_map.keys.shape[1], width, _stream())
+    return gen, dist, cand_p, cand_id
+
+
+class BeamState(object):
+    """The device-side state of one beam-search pass over B items x W slots and at most T steps: what K25 rewrites every step (``parent``,
+    ``token``, ``cum``, ``len``, ``alive``), the [T, B, W] history K27 walks back, and the finished pool (best W retired hypotheses per item)."""
+
+    def __init__(self, B, W, T, device):
+        self.B, self.W, self.T = B, W, T
+        self.alive = torch.zeros(B, W, dtype=torch.uint8, device=device)
+        self.alive[:, 0] = 1  # the root: BOS in slot 0, cost 0, length 1
+        self.cum = torch.zeros(B, W, dtype=torch.float32, device=device)
+        self.len = torch.ones(B, W, dtype=torch.int32, device=device)
+        self.parent = torch.zeros(B, W, dtype=torch.int32, device=device)
+        self.token = torch.zeros(B, W, dtype=torch.int64, device=device)
+        self.hist_parent = torch.zeros(T, B, W, dtype=torch.int32, device=device)
+        self.hist_token = torch.zeros(T, B, W, dtype=torch.int64, device=device)
+        self.fin_key = torch.full((B, W), float("inf"), dtype=torch.float32, device=device)
+        self.fin_step = torch.full((B, W), -1, dtype=torch.int32, device=device)
+        self.fin_slot = torch.zeros(B, W, dtype=torch.int32, device=device)
+
+
+def beam_advance(state, cand_p, cand_id, t, eos):
+    """K25: step ``t`` of the search on ``state`` (in place) from the candidates cand_p f32 / cand_id int64 [B * W, W] of the step's rows."""
+    B, W = state.B, state.W
+    if tuple(cand_p.shape) != (B * W, W) or tuple(cand_id.shape) != (B * W, W) or cand_p.dtype != torch.float32 or cand_id.dtype != torch.int64:
+        raise TypeError("beam_advance: candidates must be f32 / int64 [B * W, W]")
+    cand_p = cand_p if cand_p.is_contiguous() else cand_p.contiguous()
+    cand_id = cand_id if cand_id.is_contiguous() else cand_id.contiguous()
+    A.call("case_beam_advance", _ptr(cand_p), _ptr(cand_id), _ptr(state.alive), _ptr(state.cum), _ptr(state.len), _ptr(state.parent), _ptr(state.token),
+           _ptr(state.hist_parent), _ptr(state.hist_token), _ptr(state.fin_key), _ptr(state.fin_step), _ptr(state.fin_slot), t, state.T, B, W,
+           -1 if eos is None else eos, _stream())
+
+
+def beam_gather(src, dst, parent, t, valid_src=None, valid_dst=None):
+    """K26: dst[l][b * W + w, :t + 1] = src[l][b * W + parent[b, w], :t + 1] for the caches ``src`` / ``dst`` (lists of [B * W, Tmax, 2E] tensors, one
+    pair of different buffers per layer) in one launch, and the same for the bool prefix validity [B * W, Tmax] when given."""
+    B, W = parent.shape
+    n = len(src)
+    first = src[0]
+    for s, d in zip(src, dst):
+        if not (s.is_contiguous() and d.is_contiguous() and s.shape == first.shape == d.shape and s.dtype == first.dtype == d.dtype
+                and s.shape[0] == B * W):
+            raise TypeError("beam_gather: every cache must be a contiguous [B * W, Tmax, 2E] tensor of one shape and dtype")
+    if parent.dtype != torch.int32 or not parent.is_contiguous():
+        raise TypeError("beam_gather: parent must be a contiguous int32 [B, W]")
+    sp = (C.c_void_p * n)(*[x.data_ptr() for x in src])
+    dp = (C.c_void_p * n)(*[x.data_ptr() for x in dst])
+    Tmax = first.shape[1]
+    A.call("case_beam_gather", C.cast(sp, C.c_void_p), C.cast(dp, C.c_void_p), n, _ptr(parent), _ptr(_u8(valid_src)), _ptr(_u8(valid_dst)), B, W, Tmax,
+           first.shape[2] * first.element_size(), t, _stream())
+
+
+def beam_backtrack(state):
+    """K27: -> (answer int64 [B, T], beam_answers int64 [B, W, T] best first, beam_scores f32 [B, W] = cum_cost / length, +inf where empty)."""
+    B, W, T = state.B, state.W, state.T
+    dev = state.fin_key.device
+    answer = torch.empty(B, T, dtype=torch.int64, device=dev)
+    beam_answers = torch.empty(B, W, T, dtype=torch.int64, device=dev)
+    beam_scores = torch.empty(B, W, dtype=torch.float32, device=dev)
+    A.call("case_beam_backtrack", _ptr(state.hist_parent), _ptr(state.hist_token), _ptr(state.fin_key), _ptr(state.fin_step), _ptr(state.fin_slot),
+           _ptr(answer), _ptr(beam_answers), _ptr(beam_scores), B, W, T, _stream())
+    return answer, beam_answers, beam_scores
+
+
 class SortedSource(object):
     """A source map [B, S] with its device-sorted (token, position) keys, made once per batch and shared by every
     pointer scatter of that batch (one per training step; one per generated token in greedy decoding)."""
@@ -1962,6 +2047,12 @@ class SortedSource(object):
         B, S = self.ids.shape
         self.keys = torch.empty(B, S, dtype=torch.int32, device=ids.device)
         A.call("case_source_sort", _ptr(self.ids), _ptr(self.keys), B, S, V, _stream())
+
+    def expand(self, width):
+        """Every row ``width`` times in a row (the rows of one item's beam slots): the sorted keys are repeated, not sorted again."""
+        out = object.__new__(SortedSource)
+        out.ids, out.V, out.keys = self.ids.repeat_interleave(width, dim=0), self.V, self.keys.repeat_interleave(width, dim=0)
+        return out
 
     @classmethod
     def fits(cls, ids, V):

@@ -70,7 +70,8 @@ enum {
   CASE_FEAT_STEP_STATE = 1u << 14,      /* ABI 600: CaseStepState on the dropout sites and the optimizer, case_step_advance */
   CASE_FEAT_INTERACTION = 1u << 15,     /* K8 case_interaction_fwd: the dual co-attention as two kernels */
   CASE_FEAT_ATTN_DECODE_APPEND = 1u << 16, /* case_attention_decode_append: the greedy step's cache append inside the attention launch */
-  CASE_FEAT_LINEAR_SKINNY = 1u << 17      /* case_linear_skinny */
+  CASE_FEAT_LINEAR_SKINNY = 1u << 17,     /* case_linear_skinny */
+  CASE_FEAT_BEAM_DECODE = 1u << 18        /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -490,6 +491,34 @@ int case_additive_key_exp(const float* uh, void* eu, int64_t n, case_stream_t st
 int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                              const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
                              int64_t S, case_stream_t stream);
+/* Beam search around the cached decode step (the reference's common/Generations.py:112-190, per item on the device; CASE_FEAT_BEAM_DECODE).
+ * A hypothesis is slot w of item b and row b * W + w of the step's batch; W <= 8.  All four launches are asynchronous on `stream`.
+ *
+ * K24 case_pointer_head_beam: K23's row (same arguments, R = B * W rows) with a top-W tail instead of the argmax: cand_p / cand_id [R, W] = the W
+ *   largest entries of the row in descending order, the lowest id first among equals; deterministic; W = 1 gives K23's id and value bit for
+ *   bit.  gen / dist [R, V] nullable.  Same limits as K23, and W <= V.
+ * K25 case_beam_advance: one step of the search for every item, in place on the caller's state.  Candidate (w, j) of a live slot w has the key
+ *   (cum[b, w] - log(cand_p[b*W + w, j] + 1e-10)) / (len[b, w] + 1); dead slots (alive == 0) contribute +inf.  The W smallest keys -- stable
+ *   in (w, j) order -- become the new slots: parent [B, W] int32 (slot of the same item), token [B, W] int64 (PAD for a slot that is not
+ *   live afterwards), cum f32, len int32, alive u8 are rewritten; hist_parent / hist_token [T, B, W] receive row t.  A new slot whose token
+ *   is `eos`, and every new slot at t == T - 1, retires into the finished pool fin_key / fin_step / fin_slot [B, W] (ascending by key, a
+ *   newcomer behind its equals, the worst dropped; initialise to +inf / -1 / 0).  Start state: alive = cum = 0 but alive[b, 0] = 1, len = 1.
+ * K26 case_beam_gather: dst[l][b*W + w, 0 .. t] = src[l][b*W + parent[b, w], 0 .. t] for the nlayers caches [B*W, Tmax, row_bytes] named by the
+ *   HOST arrays src / dst (two different buffers per layer; row_bytes a multiple of 16, pointers 16-byte aligned) and, when given, for the
+ *   prefix validity valid_src -> valid_dst u8 [B*W, Tmax].  One launch for up to 16 layers; one launch per 16 layers beyond that.
+ * K27 case_beam_backtrack: the pool's hypotheses followed back through the history: beam_answers [B, W, T] int64 best first (BOS dropped, EOS
+ *   kept, PAD behind it), beam_scores [B, W] f32 = cum / len (+inf for an empty entry), answer [B, T] = beam_answers[:, 0]. */
+int case_pointer_head_beam(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                           int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W,
+                           case_stream_t stream);
+int case_beam_advance(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent, int64_t* token,
+                      int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step, int32_t* fin_slot, int64_t t, int64_t T,
+                      int64_t B, int32_t W, int64_t eos, case_stream_t stream);
+int case_beam_gather(const void* const* src, void* const* dst, int32_t nlayers, const int32_t* parent, const uint8_t* valid_src,
+                     uint8_t* valid_dst, int64_t B, int32_t W, int64_t Tmax, int64_t row_bytes, int64_t t, case_stream_t stream);
+int case_beam_backtrack(const int32_t* hist_parent, const int64_t* hist_token, const float* fin_key, const int32_t* fin_step,
+                        const int32_t* fin_slot, int64_t* answer, int64_t* beam_answers, float* beam_scores, int64_t B, int32_t W, int64_t T,
+                        case_stream_t stream);
 int case_pointer_attend_decode(const float* wq, const float* wq_add, const void* eu, const float* v, const void* value, const uint8_t* col_valid,
                                const uint8_t* row_valid, const float* prior, void* ctx, float* p, float* copy, int64_t B, int64_t S, int64_t H,
                                case_stream_t stream);
