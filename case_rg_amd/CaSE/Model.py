@@ -11,7 +11,7 @@ import torch.nn as nn
 from .. import config, ops
 from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
-from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder
+from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, sampling_params
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
 
@@ -57,7 +57,7 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
         return dec_out, gen, d1, d2
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
-                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None):
+                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None):
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
@@ -73,6 +73,9 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
         if beam_width:
             return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width,
                               feature_of=lambda T: self._feature(additional_decoder_feature, T))
+        if sampling:
+            return self._sample(mems, valid, weights, source_map, BOS, max_target_length, sampling,
+                                feature_of=lambda T: self._feature(additional_decoder_feature, T))
         return self._greedy(mems, valid, weights, source_map, BOS, max_target_length,
                             feature_of=lambda T: self._feature(additional_decoder_feature, T))
 
@@ -150,7 +153,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
-               span_extraction_result, output=None, max_target_length=None, beam_width=None):
+               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -165,7 +168,7 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep[0], passage_rep[0]], self.BOS, self.UNK, source_map,
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p], beam_width=beam_width)
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling)
 
 
 class CaSE(nn.Module):
@@ -187,6 +190,7 @@ class CaSE(nn.Module):
         self.vocab_size = len(id2vocab)
         self.vocab2id = vocab2id
         self.beam_width = 4  # do_beam's default width
+        self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -236,6 +240,23 @@ class CaSE(nn.Module):
                                              beam_width=self.beam_width if width is None else width)
         return {'answer': rg[3], 'rank': ps[0], 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
 
+    def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None):
+        """``do_test`` with every token DRAWN from the model's distribution (the reference's common/Generations.py ``sample`` loop; the draw is
+        from the mixed pointer-generator distribution itself after ``temperature`` / ``top_k`` (0 = off) / ``top_p`` (1 = off), not from the
+        reference's softmax of it): the ``do_test`` dict plus ``samples`` [B, N, T], ``sample_probs`` [B, N, T] (the model's unfiltered
+        probability of each drawn token, 1 behind the end) and ``sample_scores`` [B, N] (mean -log p over the emitted non-PAD tokens);
+        ``answer`` = samples[:, 0].  ``seed=None`` draws from the global counter stream (``config.next_rng``: new samples every pass, and on
+        every replay of a captured pass when a device step state is installed; without one a replay repeats its samples); an integer seed
+        gives a private, reproducible pass and leaves the global stream untouched.  ``uniforms`` f32 [T, B * N] is the kernel's ``uniforms`` override
+        handed up one layer, beyond the reference's interface: a caller with a stream of its own (antithetic or common random numbers across
+        models, a replayed draw) supplies u of row b N + n at step t as uniforms[t, b N + n]; it replaces ``seed`` and the counter generator."""
+        sampling = sampling_params(self.vocab2id, num_samples, temperature, top_k, top_p, seed, uniforms)
+        eq, ep, ps, se = self._encode_select_extract(data)
+        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                             encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
+                                             output=None, max_target_length=self.max_target_length, sampling=sampling)
+        return {'answer': rg[3], 'rank': ps[0], 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
+
     def forward(self, data, method='mle_train'):
         # the reference expands data['source_map'] into a dense one-hot here (Utils.build_map, 15 GB at cfg 2);
         # the ids themselves feed the pointer scatter kernel instead
@@ -245,3 +266,5 @@ class CaSE(nn.Module):
             return self.do_test(data)
         elif method == 'beam':
             return self.do_beam(data)
+        elif method == 'sample':
+            return self.do_sample(data, **self.sampling)

@@ -95,6 +95,22 @@ class TransformerSeqEncoder(nn.Module):
         return outs
 
 
+def sampling_params(vocab2id, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None):
+    """The checked ``sampling`` argument of the pointer decoders (what the task models' ``do_sample`` hands down)."""
+    from .Constants import EOS_WORD, PAD_WORD, UNK_WORD
+    if int(num_samples) != num_samples or num_samples < 1:
+        raise ValueError("do_sample: num_samples must be an integer >= 1, not %r" % (num_samples,))
+    if not float(temperature) > 0.0:
+        raise ValueError("do_sample: temperature must be > 0, not %r" % (temperature,))
+    if int(top_k) != top_k or top_k < 0:
+        raise ValueError("do_sample: top_k must be an integer >= 0 (0 = off), not %r" % (top_k,))
+    if not 0.0 < float(top_p) <= 1.0:
+        raise ValueError("do_sample: top_p must lie in (0, 1] (1 = off), not %r" % (top_p,))
+    return dict(num_samples=int(num_samples), temperature=float(temperature), top_k=int(top_k), top_p=float(top_p),
+                seed=None if seed is None else int(seed) & 0xFFFFFFFFFFFFFFFF, uniforms=uniforms,
+                eos=vocab2id[EOS_WORD], unk=vocab2id[UNK_WORD], pad=vocab2id[PAD_WORD])
+
+
 class PointerDecoderCore(nn.Module):
     """Shared machinery of the three pointer-generator decoders."""
 
@@ -111,6 +127,7 @@ class PointerDecoderCore(nn.Module):
         self.eos_check_every = 8
         self.last_greedy_steps = 0
         self.last_beam_steps = 0
+        self.last_sample_steps = 0
         # beam search retires a hypothesis on this id (the task models set it to EOS); None: every hypothesis runs to max_target_length
         self.beam_eos_id = None
 
@@ -285,6 +302,75 @@ class PointerDecoderCore(nn.Module):
         answer, beam_answers, beam_scores = ops.beam_backtrack(state)
         return dec_out, None, None, answer, beam_answers, beam_scores
 
+    def _sample(self, mems, valid, weights, source_map, BOS, max_target_length, params, feature_of=None):
+        """Sampled decoding over the cached step (the reference's common/Generations.py:7-63 ``sample``, with the draw on the device).  The
+        ``num_samples`` draws of an item are extra batch rows (row b * N + n), built like ``_beam``'s slots: memories, masks, copy priors, the
+        e^{2 uh} caches and the sorted source keys are repeated N times once per pass (N x the memory footprint per item).  Every step is
+        ``_greedy``'s step on B * N rows with K28 (ops.pointer_head_sample) in place of K23: one launch draws the token of every row after
+        temperature / top-k / top-p, applies the loop's conventions (UNK for EOS at step 0, EOS forced at the last step, PAD behind the end)
+        and keeps the ``ended`` flags on the device; nothing is read back inside a step.  When the fused head is not eligible the unfused
+        distribution feeds the same kernel (``dist_in``).
+
+        ``params``: dict(num_samples, temperature, top_k, top_p, eos, unk, pad, seed, uniforms).  ``uniforms`` f32 [T, B * N] overrides the
+        RNG.  Otherwise row r of step t draws at counter rng_base + offset + r: with ``seed`` None, (seed, offset, state) is
+        ``config.next_rng(B * N)`` per step -- the global counter stream, so with a device step state installed a captured pass draws NEW
+        samples on every replay whose ``CaseStepState.rng_base`` has moved, and WITHOUT a device state a replay repeats its samples (seed and
+        offsets are frozen into the graph); with an integer ``seed`` the pass is private and reproducible: (seed, offset t * B * N, no state).
+        -> (dec_out of the last step's rows, None, None, answer [B, T], samples [B, N, T], sample_probs [B, N, T], sample_scores [B, N])."""
+        B, dev, N, T = mems[0].shape[0], mems[0].device, int(params["num_samples"]), max_target_length
+        V = self.tgt_vocab_size
+        if not ops.sample_supported(V):
+            raise RuntimeError("sampled decoding: the vocabulary (%d) is beyond what the sampling kernel holds in LDS (V <= 36000)" % V)
+        if N > 1:
+            mems = [m.repeat_interleave(N, dim=0) for m in mems]
+            valid = [v.repeat_interleave(N, dim=0) for v in valid]
+            weights = None if weights is None else [w.repeat_interleave(N, dim=0) for w in weights]
+            source_map = source_map.expand(N) if isinstance(source_map, ops.SortedSource) else source_map.repeat_interleave(N, dim=0)
+        feat = None if feature_of is None else feature_of(1)
+        if feat is not None and N > 1:
+            feat = feat.repeat_interleave(N, dim=0)
+        R = B * N
+        inference, cache, self_kvs, hist_valid, splits = self._cache_setup(mems, T, feat)
+        ids = self._bos(R, BOS, dev)
+        ended = torch.zeros(R, dtype=torch.uint8, device=dev)
+        capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
+        fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, V, len(mems)))
+        seed, uniforms = params.get("seed"), params.get("uniforms")
+        if uniforms is not None and tuple(uniforms.shape) != (T, R):
+            raise ValueError("sampled decoding: uniforms must be [max_target_length, batch * num_samples] = [%d, %d]" % (T, R))
+        draw = (params["eos"], params["unk"], params["pad"], params["temperature"], params["top_k"], params["top_p"])
+        picked, probs = [], []
+        for t in range(T):
+            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid)
+            if uniforms is not None:
+                rng, u = None, uniforms[t]
+            else:
+                rng, u = (config.next_rng(R) if seed is None else (int(seed), t * R, None)), None
+            if fused_head:  # K28: vocabulary softmax, mixing, pointer scatter and the draw in one launch
+                dec_out, gen_in = self._head_parts(dec_in, x, feat)
+                logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
+                _, _, tok, p = ops.pointer_head_sample(logits, mix_logits, source_map, [c.reshape(R, -1) for c in copies], ended, t == 0, t == T - 1,
+                                                       *draw, rng=rng, uniforms=u)
+            else:  # no K23 for this pass: the unfused distribution feeds the same draw
+                dec_out, _, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
+                _, _, tok, p = ops.pointer_head_sample(None, None, None, None, ended, t == 0, t == T - 1, *draw, rng=rng, uniforms=u,
+                                                       dist_in=dist[:, -1].detach().float())
+            ids = tok.unsqueeze(1)
+            picked.append(ids)
+            probs.append(p.unsqueeze(1))
+            if not capturing and (t + 1) % self.eos_check_every == 0 and t + 1 < T and bool(ended.all()):
+                break
+        self.last_sample_steps = len(picked)
+        samples, sample_probs = torch.cat(picked, dim=1), torch.cat(probs, dim=1)
+        if samples.size(1) < T:  # every row had ended: PAD, probability 1
+            samples = torch.nn.functional.pad(samples, (0, T - samples.size(1)))
+            sample_probs = torch.nn.functional.pad(sample_probs, (0, T - sample_probs.size(1)), value=1.0)
+        emitted = samples.ne(params["pad"])
+        nll = -torch.log(sample_probs.clamp_min(1e-30)) * emitted
+        sample_scores = nll.sum(dim=1) / emitted.sum(dim=1).clamp_min(1)
+        samples = samples.view(B, N, T)
+        return dec_out, None, None, samples[:, 0].contiguous(), samples, sample_probs.view(B, N, T), sample_scores.view(B, N)
+
     def _head_logits(self, dec_out, gen_in, ctxs):
         """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 take."""
         B, V = dec_out.shape[0], self.tgt_vocab_size
@@ -366,7 +452,7 @@ class TransformerSeqDecoder(PointerDecoderCore):
         return torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None):
         source_map = self._source(source_maps) if isinstance(source_maps, (list, tuple)) else source_maps
         B = source_map.size(0)
         source_map = self._sorted(source_map)
@@ -382,4 +468,6 @@ class TransformerSeqDecoder(PointerDecoderCore):
             return None
         if beam_width:
             return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width)
+        if sampling:
+            return self._sample(mems, valid, weights, source_map, BOS, max_target_length, sampling)
         return self._greedy(mems, valid, weights, source_map, BOS, max_target_length)

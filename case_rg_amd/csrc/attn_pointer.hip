@@ -670,6 +670,346 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const Hea
   }
 }
 
+// ---- K28: the sampled step's head = K23's row with a filtered draw ------------------------------------------------------------------
+// The same row build (or a ready distribution row, `dist_in`), then one token drawn from it: q = p^(1/temperature), the order of K24 (q
+// descending, id ascending), top-k, top-p, and an inverse-CDF draw in id order with one uniform per row.  The row stays in LDS UNCHANGED: q
+// is formed from p wherever it is needed (temperature 1: q = p; otherwise 2^((log2 p - log2 pmax) / temperature), i.e. q scaled so that its
+// largest entry is 1 (v_log_f32 / v_exp_f32) -- the draw does not depend on the scale, and a low temperature cannot flush every entry to zero), so the returned
+// probability is the row's own entry and no second V-sized buffer exists.
+//
+// Selection is a radix select over the bit pattern of q (q >= 0: the pattern orders like the value), 8 bits per level, with ONE 256-bin
+// histogram of 64-bit integers in the dead key-staging area: entry counts for top-k, fixed-point masses (2^-40 of the largest entry's
+// binade) for top-p.  Integer sums do not depend on the order of the LDS atomics, so the cuts are the same on every run.  The entries that
+// equal the cut value are taken in id order up to a cut id found by a prefix count.  kept(i) <=> bits(q_i) > cut bits, or equal and i <= cut id.
+//
+// Every pass walks the row by wave: wave w owns the consecutive ids [w C, (w + 1) C) (conflict-free LDS reads).  The draw is a prefix sum
+// in that order: a lane sums four consecutive ids of a 256-id tile (one 16-byte read), a shuffle scan over the lanes' totals, a running
+// carry over the wave's tiles, the 16 wave totals summed in wave order -- a fixed summation tree of depth 3 + 7 + ceil(V / 4096) + 16, run
+// twice with the same instructions (totals, then the search), so the last prefix IS the mass Z and u Z < Z always finds a token.  (One id
+// per lane and tile made the two sweeps 19 us of dependent shuffle latency at V = 30 522; four make them a quarter of that.)  No float
+// atomics anywhere.
+constexpr int SM_WAVES = PH_THREADS / 64;
+struct SampleArgs {
+  const float* dist_in;     // [R, V] when HeadArgs.logits is null
+  const float* uniforms;    // [R] or null: overrides the counter RNG
+  const CaseStepState* state;
+  uint64_t seed, offset;
+  uint8_t* ended;           // [R] in / out
+  int64_t* ids;             // [R] the emitted token
+  float* prob;              // [R] row[drawn token]; 1 for a row that had ended
+  int64_t eos, unk, pad;
+  float temperature, top_p;
+  int top_k, first, last;
+};
+
+struct SampleView {  // how a pass sees the row: the wave's id range, the q transform, the current cut
+  const float* row;
+  int w0, w1, lane;
+  bool unit;
+  float inv_tau, l2max, scale;
+  uint32_t cbits;
+  int cid;
+  __device__ __forceinline__ float qf(float p) const {
+    if (unit) return p;
+    return p > 0.f ? __builtin_amdgcn_exp2f((__builtin_amdgcn_logf(p) - l2max) * inv_tau) : 0.f;
+  }
+  __device__ __forceinline__ float q(int i) const { return qf(row[i]); }
+  // x[0 .. 3] = the own kept mass q of each of the four consecutive ids base + 4 lane + (0 .. 3), 0 for an id the cuts dropped or one at or
+  // behind w1 (one 16-byte LDS read per lane; the row is padded to a multiple of four floats).  The caller forms the running sums.
+  __device__ __forceinline__ void quad(int base, float (&x)[4]) const {
+    const int i0 = base + 4 * lane;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) x[e] = 0.f;
+    if (i0 < w1) {
+      const float4 p4 = *reinterpret_cast<const float4*>(row + i0);
+      const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float qe = qf(p[e]);
+        if (i0 + e < w1 && kept(__float_as_uint(qe), i0 + e)) x[e] = qe;
+      }
+    }
+  }
+  __device__ __forceinline__ bool kept(uint32_t qb, int i) const { return qb > cbits || (qb == cbits && i <= cid); }
+};
+
+template <bool MASS>
+__device__ __forceinline__ void sample_hist_pass(const SampleView& v, unsigned long long* hist, uint32_t prefix, uint32_t pmask, int shift) {
+  uint32_t cb = 0;  // a thread adds a run of entries that share a digit with one atomic
+  unsigned long long acc = 0;
+  for (int base = v.w0; base < v.w1; base += 256) {  // four consecutive ids per lane: one 16-byte LDS read (the row is padded to a multiple of 4)
+    const int i0 = base + 4 * v.lane;
+    if (i0 < v.w1) {
+      const float4 p4 = *reinterpret_cast<const float4*>(v.row + i0);
+      const float p[4] = {p4.x, p4.y, p4.z, p4.w};
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        const float q = v.qf(p[e]);
+        const uint32_t qb = __float_as_uint(q);
+        if (i0 + e < v.w1 && (qb & pmask) == prefix && v.kept(qb, i0 + e)) {
+          const uint32_t d = (qb >> shift) & 255u;
+          if (d != cb) {
+            if (acc) atomicAdd(&hist[cb], acc);
+            cb = d;
+            acc = 0;
+          }
+          acc += MASS ? (unsigned long long)(q * v.scale) : 1ull;
+        }
+      }
+    }
+  }
+  if (acc) atomicAdd(&hist[cb], acc);
+}
+
+// wave 0: the digit d, highest first, with  above(d) < target <= above(d) + hist[d];  sel = {weight above the prefix, target, digit}
+__device__ __forceinline__ void sample_select(const unsigned long long* hist, unsigned long long* sel, int lane, bool set_target, double top_p) {
+  unsigned long long h[4], s = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    h[e] = hist[255 - 4 * lane - e];
+    s += h[e];
+  }
+  unsigned long long inc = s;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const unsigned long long t = __shfl_up(inc, o, 64);
+    if (lane >= o) inc += t;
+  }
+  const unsigned long long total = __shfl(inc, 63, 64);
+  unsigned long long above = sel[0], target = sel[1];
+  if (set_target) {  // top-p: the first level's histogram holds the whole mass
+    target = (unsigned long long)(top_p * (double)total);
+    if (target > total) target = total;
+    if (target < 1) target = 1;  // at least one entry
+  }
+  unsigned long long run = above + inc - s;
+  int found = -1;
+  unsigned long long found_above = 0;
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    if (found < 0 && run < target && target <= run + h[e]) {
+      found = 255 - 4 * lane - e;
+      found_above = run;
+    }
+    run += h[e];
+  }
+  const bool any = __ballot(found >= 0) != 0ull;
+  if (found >= 0) {
+    sel[0] = found_above;
+    sel[2] = (unsigned long long)found;
+  }
+  if (lane == 0) {
+    sel[1] = target;
+    if (!any) sel[2] = 0;  // an empty or all-zero row: the lowest digit, i.e. no cut
+  }
+}
+
+// the cut value: the bit pattern v with  weight(q > v) < target <= weight(q >= v)  over the kept entries; leaves sel[0] = weight(q > v), sel[1] = target
+template <bool MASS>
+__device__ __forceinline__ uint32_t sample_radix(const SampleView& v, unsigned long long* hist, unsigned long long* sel, unsigned long long target,
+                                                 double top_p) {
+  const int tid = threadIdx.x;
+  __syncthreads();
+  if (tid == 0) {
+    sel[0] = 0;
+    sel[1] = target;
+  }
+  uint32_t prefix = 0, pmask = 0;
+  for (int shift = 24; shift >= 0; shift -= 8) {
+    if (tid < 256) hist[tid] = 0;
+    __syncthreads();
+    sample_hist_pass<MASS>(v, hist, prefix, pmask, shift);
+    __syncthreads();
+    if (tid < 64) sample_select(hist, sel, tid, MASS && shift == 24, top_p);
+    __syncthreads();
+    prefix |= (uint32_t)sel[2] << shift;
+    pmask |= 255u << shift;
+  }
+  return prefix;
+}
+
+// the id of the r-th kept entry (r >= 1, id order) whose q has the bit pattern `bits`; the last id of the row when there are fewer
+__device__ __forceinline__ int sample_nth_tie(const SampleView& v, uint32_t bits, unsigned long long r, uint32_t* wcnt, int* tie_id, int V) {
+  const int wave = threadIdx.x >> 6;
+  uint32_t c = 0;
+  for (int base = v.w0; base < v.w1; base += 64) {
+    const int i = base + v.lane;
+    bool flag = false;
+    if (i < v.w1) {
+      const uint32_t qb = __float_as_uint(v.q(i));
+      flag = qb == bits && v.kept(qb, i);
+    }
+    c += (uint32_t)__popcll(__ballot(flag));
+  }
+  __syncthreads();
+  if (v.lane == 0) wcnt[wave] = c;
+  if (threadIdx.x == 0) *tie_id = V - 1;
+  __syncthreads();
+  unsigned long long off = 0;
+  for (int w = 0; w < wave; ++w) off += wcnt[w];
+  if (off < r && r <= off + c) {  // (wave-uniform) this wave holds it
+    const uint32_t need = (uint32_t)(r - off);
+    uint32_t run = 0;
+    for (int base = v.w0; base < v.w1; base += 64) {
+      const int i = base + v.lane;
+      bool flag = false;
+      if (i < v.w1) {
+        const uint32_t qb = __float_as_uint(v.q(i));
+        flag = qb == bits && v.kept(qb, i);
+      }
+      const unsigned long long m = __ballot(flag);
+      const uint32_t n = (uint32_t)__popcll(m);
+      if (run + n >= need) {
+        const unsigned long long upto = m & ((2ull << v.lane) - 1ull);  // the flags of the lanes <= this one
+        if (flag && (uint32_t)__popcll(upto) == need - run) *tie_id = i;
+        break;
+      }
+      run += n;
+    }
+  }
+  __syncthreads();
+  return *tie_id;
+}
+
+__device__ __forceinline__ float sample_scan64(float x, int lane) {  // inclusive prefix sum over the wave, fixed tree
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const float t = __shfl_up(x, o, 64);
+    if (lane >= o) x += t;
+  }
+  return x;
+}
+
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s) {
+  extern __shared__ __attribute__((aligned(16))) float ph_smem[];
+  float* row = ph_smem;
+  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
+  float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);
+  float* red = tv + PH_THREADS;
+  unsigned long long* hist = reinterpret_cast<unsigned long long*>(tk);  // [256]: the key staging is dead behind the row build
+  __shared__ unsigned long long sel[3];
+  __shared__ uint32_t wcnt[SM_WAVES];
+  __shared__ float wsum[SM_WAVES];
+  __shared__ int wmin[SM_WAVES], wmax[SM_WAVES];
+  __shared__ int tie_id;
+  const int64_t b = blockIdx.x;
+  const int V = (int)a.V, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  if (a.logits) {
+    pointer_head_build_row(a, row, tk, tv, red, b);
+  } else {
+    for (int i = tid; i < V; i += PH_THREADS) row[i] = s.dist_in[b * a.V + i];
+    __syncthreads();
+  }
+  float pmax = 0.f;
+  for (int i = tid; i < V; i += PH_THREADS) {
+    const float x = row[i];
+    if (a.dist) a.dist[b * a.V + i] = x;
+    pmax = fmaxf(pmax, x);
+  }
+  pmax = block_max(pmax, red);
+
+  SampleView v;
+  v.row = row;
+  const int chunk = (((V + SM_WAVES - 1) / SM_WAVES) + 255) & ~255;  // whole 256-id tiles: 16-byte aligned quads
+  v.w0 = min(V, wave * chunk);
+  v.w1 = min(V, v.w0 + chunk);
+  v.lane = lane;
+  v.unit = s.temperature == 1.f;
+  v.inv_tau = 1.f / s.temperature;
+  v.l2max = v.unit ? 0.f : __builtin_amdgcn_logf(pmax);
+  {
+    int e = 0;
+    frexpf(v.unit ? pmax : 1.f, &e);  // largest q < 2^e
+    v.scale = ldexpf(1.f, min(40 - e, 120));
+  }
+  v.cbits = 0;  // no cut: every entry is kept
+  v.cid = V - 1;
+
+  if (s.top_k > 0 && s.top_k < V) {
+    const uint32_t bits = sample_radix<false>(v, hist, sel, (unsigned long long)s.top_k, 0.0);
+    const unsigned long long r = sel[1] - sel[0];  // entries still to take among those that equal the cut value
+    const int id = sample_nth_tie(v, bits, r, wcnt, &tie_id, V);
+    v.cbits = bits;
+    v.cid = id;
+  }
+  if (s.top_p < 1.f) {
+    const uint32_t bits = sample_radix<true>(v, hist, sel, 0ull, (double)s.top_p);
+    const unsigned long long m = (unsigned long long)(__uint_as_float(bits) * v.scale), lack = sel[1] - sel[0];
+    const unsigned long long r = m > 0 ? (lack + m - 1) / m : 1ull;
+    const int id = sample_nth_tie(v, bits, r < 1 ? 1ull : r, wcnt, &tie_id, V);
+    v.cbits = bits;
+    v.cid = id;
+  }
+
+  // the draw: Z, then the smallest kept id whose prefix exceeds u Z.  A lane owns four consecutive ids of a 256-id tile: its running sums,
+  // the shuffle scan of the lanes' totals, the carry over the wave's tiles, the wave's offset -- the same adds in both sweeps
+  float carry = 0.f;
+  for (int base = v.w0; base < v.w1; base += 256) {
+    float x[4];
+    v.quad(base, x);
+    const float mine = ((x[0] + x[1]) + x[2]) + x[3];
+    const float inc = sample_scan64(mine, lane);
+    float before = __shfl_up(inc, 1, 64);
+    if (lane == 0) before = 0.f;
+    carry += __shfl(before + mine, 63, 64);
+  }
+  if (lane == 0) wsum[wave] = carry;
+  __syncthreads();
+  float off = 0.f, Z = 0.f;
+  for (int w = 0; w < SM_WAVES; ++w) {
+    if (w == wave) off = Z;
+    Z += wsum[w];
+  }
+  const float u = s.uniforms ? s.uniforms[b] : rng_uniform24(s.seed, rng_base_of(s.state) + s.offset + (uint64_t)b);
+  const float thr = u * Z;
+  int mn = 0x7fffffff, mx = -1;
+  carry = 0.f;
+  for (int base = v.w0; base < v.w1; base += 256) {
+    float x[4];
+    v.quad(base, x);
+    const float mine = ((x[0] + x[1]) + x[2]) + x[3];
+    const float inc = sample_scan64(mine, lane);
+    float before = __shfl_up(inc, 1, 64);
+    if (lane == 0) before = 0.f;
+    float run = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      run = e == 0 ? x[0] : run + x[e];  // (x0 + x1) + x2 ... : the association of `mine`
+      const int i = base + 4 * lane + e;
+      if (x[e] > 0.f) {  // an entry without mass is never drawn, whatever the rounding of its prefix
+        mx = i;          // (ids ascend within a lane)
+        if (off + (carry + (before + run)) > thr && i < mn) mn = i;
+      }
+    }
+    carry += __shfl(before + mine, 63, 64);
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    mn = min(mn, __shfl_xor(mn, o, 64));
+    mx = max(mx, __shfl_xor(mx, o, 64));
+  }
+  if (lane == 0) {
+    wmin[wave] = mn;
+    wmax[wave] = mx;
+  }
+  __syncthreads();
+  if (tid == 0) {
+    for (int w = 0; w < SM_WAVES; ++w) {
+      mn = min(mn, wmin[w]);
+      mx = max(mx, wmax[w]);
+    }
+    const int x = mn < V ? mn : (mx >= 0 ? mx : 0);  // rounding left none: the largest kept id with mass
+    const bool e = s.ended[b] != 0, this_end = (int64_t)x == s.eos;
+    int64_t emit;
+    if (s.first) emit = this_end ? s.unk : (int64_t)x;
+    else if (s.last) emit = e ? s.pad : s.eos;
+    else emit = e ? s.pad : (int64_t)x;
+    s.ids[b] = emit;
+    s.prob[b] = e ? 1.f : row[x];
+    s.ended[b] = (uint8_t)(e || this_end);
+  }
+}
+
 // ---- K11 ---------------------------------------------------------------------------------------
 __global__ void copy_scatter_fwd_kernel(const int64_t* __restrict__ src, const float* __restrict__ w,
                                         float* __restrict__ dist, int64_t B, int64_t Tn, int64_t S, int64_t V) {
@@ -974,6 +1314,53 @@ extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logi
   }
   hipLaunchKernelGGL(pointer_head_beam_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id, (int)W);
   return case_check_launch("case_pointer_head_beam");
+}
+
+extern "C" int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
+                                        int64_t pad, int32_t first, int32_t last, case_stream_t stream) {
+  CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "case_pointer_head_sample: bad argument");
+  CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
+               "case_pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]");
+  CASE_REQUIRE((logits != nullptr) != (dist_in != nullptr), "case_pointer_head_sample: give either the logits or a ready distribution");
+  HeadArgs a;
+  if (logits) {
+    const int rc = pointer_head_args(a, "case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+    if (rc != CASE_OK) return rc;
+  } else {
+    if (V > 36000) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_sample: built for V <= 36000");
+    a = HeadArgs();
+    a.dist = dist;
+    a.V = V;
+  }
+  SampleArgs s;
+  s.dist_in = dist_in;
+  s.uniforms = uniforms;
+  s.state = state;
+  s.seed = seed;
+  s.offset = offset;
+  s.ended = ended;
+  s.ids = ids;
+  s.prob = prob;
+  s.eos = eos;
+  s.unk = unk;
+  s.pad = pad;
+  s.temperature = temperature;
+  s.top_p = top_p;
+  s.top_k = top_k;
+  s.first = first;
+  s.last = last;
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
+        hipSuccess)
+      return case_set_error(CASE_E_LAUNCH, "case_pointer_head_sample: cannot reserve LDS");
+    attr = true;
+  }
+  hipLaunchKernelGGL(pointer_head_sample_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s);
+  return case_check_launch("case_pointer_head_sample");
 }
 
 extern "C" int case_copy_scatter_fwd(const int64_t* src, const float* w, float* dist, int64_t B, int64_t T, int64_t S,

@@ -165,6 +165,11 @@ __device__ __forceinline__ void rng_uniform2(uint64_t seed, uint64_t idx_even, f
   u0 = (float)(h & 0xffffu) * (1.0f / 65536.0f);
   u1 = (float)(h >> 16) * (1.0f / 65536.0f);
 }
+// 24-bit uniform in [0, 1) from ONE full hash per counter: the draw of a sampled token (K28) must resolve probabilities far below the
+// 1 / 65536 of the dropout uniforms (1.5e-5 is an ordinary token probability at V = 30 522)
+__device__ __forceinline__ float rng_uniform24(uint64_t seed, uint64_t counter) {
+  return (float)(rng_hash(seed, counter) >> 8) * (1.0f / 16777216.0f);
+}
 // keep-or-zero for 8 consecutive elements starting at idx0 (any parity)
 __device__ __forceinline__ void dropout8(float (&x)[8], uint64_t seed, uint64_t idx0, float p, float scale) {
   if ((idx0 & 1) == 0) {

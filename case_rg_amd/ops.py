@@ -1974,6 +1974,58 @@ def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=Fa
     return gen, dist, cand_p, cand_id
 
 
+def sample_supported(V):
+    return V <= 36000 and bool(A.lib.case_abi_features() & A.FEAT_SAMPLE_DECODE)
+
+
+def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, t_last, eos, unk, pad, temperature, top_k, top_p, rng=None,
+                        uniforms=None, dist_in=None, want_gen=False, want_dist=False):
+    """K28, ``pointer_head_decode`` with a draw instead of the argmax: -> (gen [R, V] | None, dist [R, V] | None, ids int64 [R], prob f32 [R]).
+    One token per row is drawn from the mixed distribution after temperature, top-k and top-p (the rule: include/case_hip.h); ``ids`` is what
+    the reference's ``sample`` loop emits for it (UNK for EOS at the first step, EOS at the last, PAD behind the end) and ``ended`` (uint8 [R])
+    is updated in place; ``prob`` is the row's unfiltered probability of the drawn token, 1 for a row that had ended.  The uniform of row r is
+    ``uniforms[r]`` (f32 [R]) when given, else the 24-bit counter uniform of ``rng = (seed, offset, state)`` (what ``config.next_rng(R)`` returns)
+    at counter ``rng_base + offset + r``.  ``dist_in`` f32 [R, V] with ``logits=None`` draws from a ready distribution instead of building the row
+    (``mix_logits`` / ``source_map`` / ``copies`` unused).  No autograd (inference)."""
+    if not (float(temperature) > 0.0) or int(top_k) < 0 or not (0.0 < float(top_p) <= 1.0):
+        raise ValueError("pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]")
+    if (logits is None) == (dist_in is None):
+        raise ValueError("pointer_head_sample: give either the logits or dist_in")
+    if uniforms is None and rng is None:
+        raise ValueError("pointer_head_sample: give rng=(seed, offset, state) or uniforms")
+    src = dist_in if logits is None else logits
+    if src.dtype != torch.float32 or src.dim() != 2:
+        raise TypeError("pointer_head_sample: the row source must be f32 [R, V]")
+    R, V = src.shape
+    dev = src.device
+    src = src if src.is_contiguous() else src.contiguous()
+    if ended.dtype != torch.uint8 or tuple(ended.shape) != (R,) or not ended.is_contiguous():
+        raise TypeError("pointer_head_sample: ended must be a contiguous uint8 [R]")
+    if uniforms is not None:
+        if uniforms.dtype != torch.float32 or tuple(uniforms.shape) != (R,):
+            raise TypeError("pointer_head_sample: uniforms must be f32 [R]")
+        uniforms = uniforms if uniforms.is_contiguous() else uniforms.contiguous()
+    seed, offset, state = rng if rng is not None else (0, 0, None)
+    gen = torch.empty(R, V, dtype=torch.float32, device=dev) if (want_gen and logits is not None) else None
+    dist = torch.empty(R, V, dtype=torch.float32, device=dev) if want_dist else None
+    ids = torch.empty(R, dtype=torch.int64, device=dev)
+    prob = torch.empty(R, dtype=torch.float32, device=dev)
+    tail = (_ptr(gen), _ptr(dist), _ptr(ids), _ptr(prob), _ptr(ended), _ptr(uniforms), R, V)
+    draw = (float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), int(seed), int(offset), state, int(eos), int(unk), int(pad),
+            int(bool(t_first)), int(bool(t_last)), _stream())
+    if logits is None:
+        A.call("case_pointer_head_sample", None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw)
+    else:
+        mix_logits = mix_logits.float().contiguous()
+        cs = [c.float().contiguous() for c in copies]
+        n = len(cs)
+        ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
+        lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
+        A.call("case_pointer_head_sample", _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
+               None, *tail, source_map.keys.shape[1], *draw)
+    return gen, dist, ids, prob
+
+
 class BeamState(object):
     """The device-side state of one beam-search pass over B items x W slots and at most T steps: what K25 rewrites every step (``parent``,
     ``token``, ``cum``, ``len``, ``alive``), the [T, B, W] history K27 walks back, and the finished pool (best W retired hypotheses per item)."""

@@ -71,7 +71,8 @@ enum {
   CASE_FEAT_INTERACTION = 1u << 15,     /* K8 case_interaction_fwd: the dual co-attention as two kernels */
   CASE_FEAT_ATTN_DECODE_APPEND = 1u << 16, /* case_attention_decode_append: the greedy step's cache append inside the attention launch */
   CASE_FEAT_LINEAR_SKINNY = 1u << 17,     /* case_linear_skinny */
-  CASE_FEAT_BEAM_DECODE = 1u << 18        /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
+  CASE_FEAT_BEAM_DECODE = 1u << 18,       /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
+  CASE_FEAT_SAMPLE_DECODE = 1u << 19      /* K28 case_pointer_head_sample */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -519,6 +520,26 @@ int case_beam_gather(const void* const* src, void* const* dst, int32_t nlayers, 
 int case_beam_backtrack(const int32_t* hist_parent, const int64_t* hist_token, const float* fin_key, const int32_t* fin_step,
                         const int32_t* fin_slot, int64_t* answer, int64_t* beam_answers, float* beam_scores, int64_t B, int32_t W, int64_t T,
                         case_stream_t stream);
+/* K28 case_pointer_head_sample (CASE_FEAT_SAMPLE_DECODE): K23's row (same arguments and limits, R rows) with one token DRAWN from it instead of
+ * the argmax.  With logits == NULL the row is read from dist_in [R, V] instead of being built (mix_logits / keys / copies / lens / gen unused,
+ * V <= 36000).  The draw rule, per row p[0 .. V) and one uniform u in [0, 1):
+ *   1. q_i = p_i^(1 / temperature), 0 where p_i = 0 (temperature 1: q = p bit for bit; otherwise q is scaled so that its largest entry is 1);
+ *   2. the order is K24's: q descending, the lower id first among equals;
+ *   3. top_k > 0 keeps the first min(top_k, V) entries of the order;
+ *   4. top_p < 1 keeps, among those, the shortest prefix of the order whose mass is >= top_p x the mass after step 3 (at least one entry);
+ *   5. with Z the kept mass, the token is the smallest kept id j, in ID order, with sum_{kept i <= j} q_i > u Z (the largest kept id with
+ *      q > 0 if rounding leaves none); an entry with q = 0 is never drawn;
+ *   6. prob [R] = p_j.
+ * u = uniforms[r] when uniforms is given, else (hash(seed, state->rng_base + offset + r) >> 8) 2^-24 (state nullable, as on a dropout site:
+ * with a device state a captured launch draws anew whenever rng_base has moved).  Deterministic: the same inputs and u give the same id.
+ * Loop conventions of the reference's common/Generations.py `sample`, on ended u8 [R] (in / out) with x the drawn id and e = ended[r]:
+ * ids[r] = first ? (x == eos ? unk : x) : last ? (e ? pad : eos) : (e ? pad : x); prob[r] = 1 where e; then ended[r] |= (x == eos).
+ * gen / dist [R, V] nullable as in K23 (dist is the unfiltered row). */
+int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                             int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob, uint8_t* ended,
+                             const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                             uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
+                             case_stream_t stream);
 int case_pointer_attend_decode(const float* wq, const float* wq_add, const void* eu, const float* v, const void* value, const uint8_t* col_valid,
                                const uint8_t* row_valid, const float* prior, void* ctx, float* p, float* copy, int64_t B, int64_t S, int64_t H,
                                case_stream_t stream);
