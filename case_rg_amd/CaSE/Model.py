@@ -57,10 +57,14 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
         return dec_out, gen, d1, d2
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
-                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None):
+                encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
+                score_index=None):
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
+        if score_index is not None:
+            return self._score(mems, valid, weights, source_map, BOS, score_index,
+                               feature_of=lambda T: self._feature(additional_decoder_feature, T))
         if max_target_length is None:
             max_target_length = groundtruth_index.size(1)
         bos = self._bos(B, BOS, mems[0].device)
@@ -153,7 +157,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
-               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None):
+               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -168,7 +172,7 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep[0], passage_rep[0]], self.BOS, self.UNK, source_map,
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling)
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index)
 
 
 class CaSE(nn.Module):
@@ -257,6 +261,25 @@ class CaSE(nn.Module):
                                              output=None, max_target_length=self.max_target_length, sampling=sampling)
         return {'answer': rg[3], 'rank': ps[0], 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
+    def do_score(self, data, answers=None):
+        """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at
+        the positions that are not scored -- the layout of ``data['response']`` (the default), of ``do_beam``'s ``beam_answers`` and of
+        ``do_sample``'s ``samples``; T' is bounded by the decoder's position table, not by ``max_target_length``.  The encoder, selection and
+        token-identification stages run once per item as in ``do_test``; the N candidates of an item are extra decoder rows (N x the memory
+        footprint).  -> ``rank`` as in ``do_test``; ``token_probs`` f32 [B, N, T'] = p(y_t | y_<t, item) under the mixed pointer-generator
+        distribution (1 where y_t is PAD); ``copy_probs`` its pointer part (0 where PAD); ``scores`` [B, N] = the mean over the non-PAD
+        targets of -log max(p, 1e-30) (``sample_scores``' convention); ``loss`` [1] = ``do_train``'s generation loss with dropout off
+        (sum of -log(p + 1e-8) over the non-PAD targets / their count); ``tokens`` = that count (int64 scalar).  A 2-D ``answers`` gives
+        N = 1.  Under no_grad the head is K29 (no vocabulary row is built); with grad enabled the pass is differentiable."""
+        if self.training:
+            raise ValueError("do_score runs in eval mode: call model.eval() first")
+        eq, ep, ps, se = self._encode_select_extract(data)
+        out = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
+                                              output=None, score_index=data['response'] if answers is None else answers)
+        out['rank'] = ps[0]
+        return out
+
     def forward(self, data, method='mle_train'):
         # the reference expands data['source_map'] into a dense one-hot here (Utils.build_map, 15 GB at cfg 2);
         # the ids themselves feed the pointer scatter kernel instead
@@ -268,3 +291,5 @@ class CaSE(nn.Module):
             return self.do_beam(data)
         elif method == 'sample':
             return self.do_sample(data, **self.sampling)
+        elif method == 'score':
+            return self.do_score(data)

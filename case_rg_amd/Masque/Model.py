@@ -44,10 +44,12 @@ class MasqueTransformerSeqDecoder(PointerDecoderCore):
         return self._head(dec_in, x, ctxs, copies, None, source_map)
 
     def forward(self, encode_memories, BOS, UNK, source_map, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
+        if score_index is not None:
+            return self._score(mems, valid, weights, source_map, BOS, score_index)
         if max_target_length is None:
             max_target_length = groundtruth_index.size(1)
         bos = self._bos(B, BOS, mems[0].device)
@@ -107,7 +109,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query=None, encode_passage=None, passage_selection_result=None,
-               output=None, max_target_length=None, beam_width=None, sampling=None):
+               output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
         if encode_query is None:
             encode_query = self.query_encoder(query)[0][:, :, -1]
         if encode_passage is None:
@@ -121,7 +123,7 @@ class ResponseGeneration(nn.Module):
         prior_p = torch.sigmoid(passage_score).unsqueeze(-1).expand(-1, -1, passage_rep.size(2))
         return self.decoder([query_rep, passage_rep], self.BOS, self.UNK, source_map, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling)
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index)
 
 
 class Masque(nn.Module):
@@ -203,6 +205,19 @@ class Masque(nn.Module):
                                              output=None, max_target_length=self.max_target_length, sampling=sampling)
         return {'answer': rg[3], 'rank': ps[0], 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
+    def do_score(self, data, answers=None):
+        """The probability of given answers under the model (eval mode only; see CaSE.do_score): ``answers`` int64 [B, T'] or [B, N, T'],
+        PAD (0) = not scored, default ``data['response']`` -> ``rank``, ``token_probs`` / ``copy_probs`` [B, N, T'], ``scores`` [B, N],
+        ``loss`` [1] (``do_train``'s generation loss with dropout off) and ``tokens``."""
+        if self.training:
+            raise ValueError("do_score runs in eval mode: call model.eval() first")
+        eq, ep, ps = self._encode_select(data)
+        out = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                              encode_passage=ep, passage_selection_result=ps, output=None,
+                                              score_index=data['response'] if answers is None else answers)
+        out['rank'] = ps[0]
+        return out
+
     def forward(self, data, method='mle_train'):
         if method == 'train':
             return self.do_train(data)
@@ -214,3 +229,5 @@ class Masque(nn.Module):
             return self.do_beam(data)
         elif method == 'sample':
             return self.do_sample(data, **self.sampling)
+        elif method == 'score':
+            return self.do_score(data)

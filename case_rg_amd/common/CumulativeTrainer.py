@@ -12,6 +12,7 @@ prediction lists.  What differs (none of it changes the numbers):
   * ``save_checkpoint`` / ``load_checkpoint`` write what a resume needs next to the reference's weights-only
     ``<epoch>.pkl`` (:80-86): optimizer moments + step, scheduler, EMA shadow, the accumulation counter and the RNG streams.
 """
+import math
 import os
 import sys
 import time
@@ -246,3 +247,25 @@ class CumulativeTrainer(object):
             for data in DevicePrefetcher(self._loader(dataset, collate_fn, batch_size, False)):
                 rs.append([data, self.model(data, method=method)])
         return rs
+
+    def evaluate_nll(self, dataset, collate_fn, batch_size):
+        """Teacher-forced negative log-likelihood of ``dataset``'s responses (``model(data, method='score')`` per batch): dict(nll = the
+        token-weighted corpus mean of the batches' ``loss``, perplexity = exp(nll), tokens = the non-PAD targets counted).  One process, under
+        no_grad in eval mode; the model's mode is restored afterwards."""
+        was_training = self.model.training
+        self.model.eval()
+        total, tokens = None, None
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    out = self.model(data, method='score')
+                    part, n = out['loss'].double().sum() * out['tokens'], out['tokens']
+                    total, tokens = (part, n) if total is None else (total + part, tokens + n)
+        finally:
+            self.model.train(was_training)
+        if total is None or int(tokens) == 0:
+            return dict(nll=float('nan'), perplexity=float('nan'), tokens=0)
+        nll = float(total) / int(tokens)  # (the one read-back of the evaluation)
+        return dict(nll=nll, perplexity=math.exp(nll), tokens=int(tokens))

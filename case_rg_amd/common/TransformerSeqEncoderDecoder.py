@@ -130,6 +130,9 @@ class PointerDecoderCore(nn.Module):
         self.last_sample_steps = 0
         # beam search retires a hypothesis on this id (the task models set it to EOS); None: every hypothesis runs to max_target_length
         self.beam_eos_id = None
+        # the head of a scoring pass (``_score``) runs over chunks of at most this many (candidate, position) rows: the f32 logits buffer is
+        # score_chunk_rows x V however many candidates are scored
+        self.score_chunk_rows = 2048
 
     # ------------------------------------------------------------------------------------------
     def _prepare(self, encode_memories, encode_masks, encode_weights, batch_size):
@@ -371,6 +374,83 @@ class PointerDecoderCore(nn.Module):
         samples = samples.view(B, N, T)
         return dec_out, None, None, samples[:, 0].contiguous(), samples, sample_probs.view(B, N, T), sample_scores.view(B, N)
 
+    def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None):
+        """Teacher-forced scoring of given answers (eval mode): ``answers`` int64 [B, T'] or [B, N, T'], ``pad`` marking the positions that
+        are not scored.  One full-prefix pass over dec_ids = cat[BOS, answers[:, :-1]] (``_run_prefix``, causal), then the head over row
+        chunks of at most ``score_chunk_rows`` (candidate, position) rows.  The N candidates of an item are extra batch rows (row b * N + n),
+        built like ``_beam``'s slots: memories, masks and copy priors are repeated N times, so a pass costs N x the memory footprint per item.
+        The sorted source keys are NOT repeated: the rows of an item are consecutive and K29 reads key row r // rows_per_source.
+        Under no_grad (and unless CASE_POINTER_SCORE=off) a chunk's head is ``_head_logits`` + K29 (ops.pointer_head_score): one read of the
+        logits, no [rows, V] distribution.  With grad enabled it is the unfused differentiable chain of the training branch (``_generate``,
+        ``_mix``, a gather), so gradients reach the parameters.  Nothing is read back: the pass captures into one graph.
+        -> dict(token_probs [B, N, T'] (1 where PAD), copy_probs [B, N, T'] (the pointer part, 0 where PAD), scores [B, N] (mean over the
+        scored targets of -log max(p, 1e-30)), loss [1] (sum of -log(p + 1e-8) over the scored targets / their count), tokens int64 scalar)."""
+        if self.training:
+            raise ValueError("scoring runs in eval mode: call model.eval() first")
+        if answers.dim() == 2:
+            answers = answers.unsqueeze(1)
+        if answers.dim() != 3 or answers.dtype != torch.int64 or answers.size(0) != mems[0].shape[0]:
+            raise ValueError("scoring: answers must be int64 [B, T] or [B, N, T] with the batch's B")
+        B, N, T = answers.shape
+        dev, V, H = mems[0].device, self.tgt_vocab_size, self.hidden_size
+        if T > self.embedding[1].pe.size(0):
+            raise RuntimeError("max_target_length %d exceeds max_len %d" % (T, self.embedding[1].pe.size(0)))
+        if N > 1:
+            mems = [m.repeat_interleave(N, dim=0) for m in mems]
+            valid = [v.repeat_interleave(N, dim=0) for v in valid]
+            weights = None if weights is None else [w.repeat_interleave(N, dim=0) for w in weights]
+        feat = None if feature_of is None else feature_of(T)
+        if feat is not None and N > 1:
+            feat = feat.repeat_interleave(N, dim=0)
+        R = B * N
+        tgt = answers.reshape(R, T).to(dev)
+        dec_ids = torch.cat([self._bos(R, BOS, dev), tgt[:, :-1]], dim=-1)
+        dec_in, x, ctxs, copies = self._run_prefix(dec_ids, mems, valid, weights, feat)
+        # every (candidate, position) pair is one row of the head; item b owns rows b * per .. (b + 1) * per - 1
+        rows, per = R * T, N * T
+        dec_in, x = dec_in.reshape(rows, 1, H), x.reshape(rows, 1, H)
+        feat = None if feat is None else feat.reshape(rows, 1, -1)
+        ctxs = [c.reshape(rows, 1, -1) for c in ctxs]
+        copies = [c.reshape(rows, -1) for c in copies]
+        flat = tgt.reshape(rows)
+        sorted_src = isinstance(source_map, ops.SortedSource)
+        fused = sorted_src and ops.pointer_score_supported(source_map, len(mems))
+        limit = max(1, int(self.score_chunk_rows))
+        if per <= limit:  # whole items per chunk
+            step = limit // per * per
+            chunks = [(r0, min(r0 + step, rows)) for r0 in range(0, rows, step)]
+        else:  # an item's rows in several chunks: every chunk lies inside one item
+            chunks = [(b * per + o, min(b * per + o + limit, (b + 1) * per)) for b in range(B) for o in range(0, per, limit)]
+        probs, ptrs = [], []
+        for r0, r1 in chunks:
+            n = r1 - r0
+            dec_out, gen_in = self._head_parts(dec_in[r0:r1], x[r0:r1], None if feat is None else feat[r0:r1])
+            cx, cp, y = [c[r0:r1] for c in ctxs], [c[r0:r1] for c in copies], flat[r0:r1]
+            b0, b1 = r0 // per, (r1 + per - 1) // per
+            if fused:  # K29: (max, sum) over the logits row, logit[y], and the pointer mass of y's run in the item's sorted keys
+                logits, mix_logits = self._head_logits(dec_out, gen_in, cx)
+                p, c = ops.pointer_head_score(logits, mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, pad)
+            else:  # the differentiable chain: every row a batch row of one position, its item's source beside it
+                item = torch.arange(r0, r1, device=dev) // per
+                src = source_map.select(item) if sorted_src else source_map.index_select(0, item)
+                gen = self._generate(gen_in, 0.0)
+                d1, d2 = self._mix(dec_out, cx, gen, [c.unsqueeze(1) for c in cp], src)
+                inside = (y >= 0) & (y < V)
+                at = y.clamp(0, V - 1).reshape(n, 1, 1)
+                c = d2.gather(-1, at).reshape(n)
+                p = d1.gather(-1, at).reshape(n) + c
+                skip = y.eq(pad) if pad >= 0 else torch.zeros_like(inside)
+                p = torch.where(skip, torch.ones_like(p), torch.where(inside, p, torch.zeros_like(p)))
+                c = torch.where(skip | ~inside, torch.zeros_like(c), c)
+            probs.append(p)
+            ptrs.append(c)
+        p, c = torch.cat(probs).view(B, N, T), torch.cat(ptrs).view(B, N, T)
+        scored = (answers.to(dev).ne(pad) if pad >= 0 else torch.ones_like(answers, dtype=torch.bool, device=dev))
+        count = scored.sum()
+        scores = (-torch.log(p.clamp_min(1e-30)) * scored).sum(dim=-1) / scored.sum(dim=-1).clamp_min(1)
+        loss = ((-torch.log(p + 1e-8) * scored).sum() / count.clamp_min(1)).reshape(1)
+        return dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
+
     def _head_logits(self, dec_out, gen_in, ctxs):
         """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 take."""
         B, V = dec_out.shape[0], self.tgt_vocab_size
@@ -452,11 +532,13 @@ class TransformerSeqDecoder(PointerDecoderCore):
         return torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
         source_map = self._source(source_maps) if isinstance(source_maps, (list, tuple)) else source_maps
         B = source_map.size(0)
         source_map = self._sorted(source_map)
         mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
+        if score_index is not None:
+            return self._score(mems, valid, weights, source_map, BOS, score_index)
         if max_target_length is None:
             max_target_length = groundtruth_index.size(1)
         bos = self._bos(B, BOS, mems[0].device)

@@ -1010,6 +1010,142 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
   }
 }
 
+// ---- K29: the head of a teacher-forced SCORING pass: one probability per row, no vocabulary row -------------------------------------------
+// prob[r] = pm_0 softmax(logits[r])[y] + sum_k pm_{1+k} sum_{positions s of memory k whose source id is y} copy_k[r, s],  y = targets[r].
+// One workgroup of 256 threads per row.  The logits row is read ONCE with a per-thread online (max, sum): 16-byte loads over the aligned
+// body, scalar peels before and behind it (V = 30 522 leaves rows 8-byte aligned, an odd V 4-byte aligned).  The stream is read
+// NON-TEMPORAL for K22's reason: every byte is used once and the buffer is rewritten by the next row chunk's vocabulary GEMM, so it should
+// not displace that GEMM's weights (the reusable data) from the caches.  -DCASE_STREAM_DEFAULT_POLICY: default policy (A/B).
+// The (max, sum) pairs meet in a fixed xor tree per wave and in wave order across the four waves; logit[y] is one direct load.  Pointer
+// mass: wave 0 finds the lower bound of y << 15 in the row's sorted keys (every lane the same search), lane l takes entries lo + l,
+// lo + l + 64, ... of the run of equal tokens, and the lanes meet in the same fixed tree.  No atomics, no LDS beyond 8 floats: V is
+// limited by the key format alone, and two launches give the same bits.
+constexpr int PS_THREADS = 256;
+struct ScoreArgs {
+  const float* logits;      // [R, V]
+  const float* mix_logits;  // [R, 1 + nmem]
+  const uint32_t* keys;     // [R / rows_per_source, S] sorted (token << 15 | position), 0xFFFFFFFF = no token
+  const float* copy[PH_MAX_MEM];  // copy_k [R, len_k]
+  int64_t len[PH_MAX_MEM];
+  const int64_t* targets;   // [R]
+  float* prob;              // [R]
+  float* ptr;               // [R] or null: the pointer part of prob
+  int64_t V, S, rows_per_source, pad;
+  int nmem;
+};
+
+typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
+#ifndef CASE_STREAM_DEFAULT_POLICY
+#define PS_LOAD1(P) __builtin_nontemporal_load(P)
+#define PS_LOAD4(P) __builtin_nontemporal_load(reinterpret_cast<const ps_f32x4*>(P))
+#else
+#define PS_LOAD1(P) (*(P))
+#define PS_LOAD4(P) (*reinterpret_cast<const ps_f32x4*>(P))
+#endif
+
+// (m, s) <- (m, s) (+) (om, os) with s = sum exp(x - m); an empty side is (-inf, 0)
+__device__ __forceinline__ void ps_merge(float& m, float& s, const float om, const float os) {
+  const float M = fmaxf(m, om);
+  const float ref = M == -INFINITY ? 0.f : M;  // both sides empty: exp(-inf - 0) = 0, never inf - inf
+  s = s * __expf(m - ref) + os * __expf(om - ref);
+  m = M;
+}
+
+__global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const ScoreArgs a) {
+  __shared__ float red_m[PS_THREADS / 64], red_s[PS_THREADS / 64];
+  const int64_t r = blockIdx.x, V = a.V;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t y = a.targets[r];
+  const bool is_pad = a.pad >= 0 && y == a.pad;
+  if (is_pad || y < 0 || y >= V) {  // (uniform over the workgroup) PAD: not scored, p = 1; an id outside the vocabulary: p = 0
+    if (tid == 0) {
+      a.prob[r] = is_pad ? 1.f : 0.f;
+      if (a.ptr) a.ptr[r] = 0.f;
+    }
+    return;
+  }
+  const float* lg = a.logits + r * V;
+  int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
+  if (head > V) head = V;
+  const int64_t n4 = (V - head) >> 2, tail = head + 4 * n4;
+  float m = -INFINITY, s = 0.f;
+  if (tid < head) ps_merge(m, s, PS_LOAD1(lg + tid), 1.f);
+  const float* body = lg + head;
+#pragma unroll 2
+  for (int64_t i = tid; i < n4; i += PS_THREADS) {
+    const ps_f32x4 x = PS_LOAD4(body + 4 * i);
+    const float m4 = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
+    if (m4 > m) {
+      s *= __expf(m - m4);  // (m = -inf: s = 0 stays 0)
+      m = m4;
+    }
+    s += (__expf(x[0] - m) + __expf(x[1] - m)) + (__expf(x[2] - m) + __expf(x[3] - m));
+  }
+  if (tail + tid < V) ps_merge(m, s, PS_LOAD1(lg + tail + tid), 1.f);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
+    ps_merge(m, s, om, os);
+  }
+  if (lane == 0) {
+    red_m[tid >> 6] = m;
+    red_s[tid >> 6] = s;
+  }
+  __syncthreads();
+  if (tid >= 64) return;  // wave 0 finishes the row
+  m = red_m[0];
+  s = red_s[0];
+#pragma unroll
+  for (int w = 1; w < PS_THREADS / 64; ++w) ps_merge(m, s, red_m[w], red_s[w]);
+  const float gen_y = __expf(lg[y] - m) / s;
+  // the mixing probabilities, as in pointer_head_build_row
+  float pm[1 + PH_MAX_MEM];
+  {
+    float mm = -INFINITY, ss = 0.f;
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) pm[k] = k <= a.nmem ? a.mix_logits[r * (a.nmem + 1) + k] : -INFINITY;
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) mm = fmaxf(mm, pm[k]);
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) {
+      pm[k] = __expf(pm[k] - mm);
+      ss += pm[k];
+    }
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) pm[k] /= ss;
+  }
+  const uint32_t* keys = a.keys + (r / a.rows_per_source) * a.S;
+  const uint32_t want = (uint32_t)y << 15;  // y < V <= 131071: fits
+  int64_t lo = 0, hi = a.S;
+  while (lo < hi) {  // the first entry with key >= y << 15 (uniform over the wave)
+    const int64_t mid = (lo + hi) >> 1;
+    if (keys[mid] < want) lo = mid + 1;
+    else hi = mid;
+  }
+  float acc = 0.f;
+  for (int64_t i = lo + lane; i < a.S; i += 64) {
+    const uint32_t key = keys[i];
+    if (key == 0xFFFFFFFFu || (key >> 15) != (uint32_t)y) break;  // the run of y has ended (keys ascend)
+    int64_t pos = key & 0x7FFFu;
+    bool done = false;
+#pragma unroll
+    for (int k = 0; k < PH_MAX_MEM; ++k) {
+      if (k < a.nmem && !done) {
+        if (pos < a.len[k]) {
+          acc += pm[k + 1] * a.copy[k][r * a.len[k] + pos];
+          done = true;
+        }
+        pos -= a.len[k];
+      }
+    }
+  }
+  acc = wave_sum(acc);
+  if (lane == 0) {
+    a.prob[r] = pm[0] * gen_y + acc;
+    if (a.ptr) a.ptr[r] = acc;
+  }
+}
+
 // ---- K11 ---------------------------------------------------------------------------------------
 __global__ void copy_scatter_fwd_kernel(const int64_t* __restrict__ src, const float* __restrict__ w,
                                         float* __restrict__ dist, int64_t B, int64_t Tn, int64_t S, int64_t V) {
@@ -1361,6 +1497,39 @@ extern "C" int case_pointer_head_sample(const float* logits, const float* mix_lo
   }
   hipLaunchKernelGGL(pointer_head_sample_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s);
   return case_check_launch("case_pointer_head_sample");
+}
+
+extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                       const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                       float* prob, float* copy, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && targets && prob && R > 0 && V > 0 && S > 0 && nmem >= 1 && R < (1ll << 31),
+               "case_pointer_head_score: bad argument");
+  CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "case_pointer_head_score: %lld rows are no multiple of rows_per_source %lld",
+               (long long)R, (long long)rows_per_source);
+  if (nmem > PH_MAX_MEM || V > 131071 || S > 32768)
+    return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_score: built for <= %d memories, V <= 131071, S <= 32768", PH_MAX_MEM);
+  ScoreArgs a;
+  a.logits = logits;
+  a.mix_logits = mix_logits;
+  a.keys = keys;
+  int64_t total = 0;
+  for (int m = 0; m < PH_MAX_MEM; ++m) {
+    a.copy[m] = m < nmem ? copies[m] : nullptr;
+    a.len[m] = m < nmem ? lens[m] : 0;
+    total += a.len[m];
+    CASE_REQUIRE(m >= nmem || (copies[m] && lens[m] > 0), "case_pointer_head_score: null copy weights");
+  }
+  CASE_REQUIRE(total == S, "case_pointer_head_score: the memories hold %lld positions, the source map %lld", (long long)total, (long long)S);
+  a.targets = targets;
+  a.prob = prob;
+  a.ptr = copy;
+  a.V = V;
+  a.S = S;
+  a.rows_per_source = rows_per_source;
+  a.pad = pad;
+  a.nmem = nmem;
+  hipLaunchKernelGGL(pointer_head_score_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
+  return case_check_launch("case_pointer_head_score");
 }
 
 extern "C" int case_copy_scatter_fwd(const int64_t* src, const float* w, float* dist, int64_t B, int64_t T, int64_t S,

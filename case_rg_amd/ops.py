@@ -2026,6 +2026,49 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     return gen, dist, ids, prob
 
 
+# K29: the head of a teacher-forced scoring pass (one probability per row, no vocabulary row).  "auto": a device-sorted source map, <= 4
+# memories, no grad; "off": the unfused differentiable chain (masked_softmax, p0 x gen, sorted scatter, add, gather).
+POINTER_SCORE = os.environ.get("CASE_POINTER_SCORE", "auto")
+
+
+def pointer_score_supported(source_map, nmem):
+    return (POINTER_SCORE != "off" and isinstance(source_map, SortedSource) and 1 <= nmem <= 4
+            and not torch.is_grad_enabled()  # (no autograd Function behind K29)
+            and bool(A.lib.case_abi_features() & A.FEAT_POINTER_SCORE))
+
+
+def pointer_head_score(logits, mix_logits, source_map, rows_per_source, copies, targets, pad=0):
+    """K29: logits f32 [R, V]; mix_logits f32 [R, 1 + nmem]; source_map a SortedSource with R / rows_per_source rows (row r reads key row
+    r // rows_per_source); copies: list of f32 [R, len_k]; targets int64 [R] -> (prob f32 [R], copy f32 [R]): the mixed pointer-generator
+    probability of every row's target and its pointer part.  ``targets == pad`` (pad -1: none) gives (1, 0), an id outside [0, V) (0, 0).
+    No autograd (inference)."""
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("pointer_head_score: logits must be f32 [R, V]")
+    R, V = logits.shape
+    rows_per_source = int(rows_per_source)
+    keys = source_map.keys
+    if rows_per_source < 1 or R % rows_per_source or keys.shape[0] * rows_per_source != R:
+        raise ValueError("pointer_head_score: %d rows, %d key rows, rows_per_source %d" % (R, keys.shape[0], rows_per_source))
+    if targets.dtype != torch.int64 or targets.numel() != R:
+        raise TypeError("pointer_head_score: targets must be int64 [R]")
+    logits = logits if logits.is_contiguous() else logits.contiguous()
+    mix_logits = mix_logits.float().contiguous()
+    if tuple(mix_logits.shape) != (R, len(copies) + 1):
+        raise ValueError("pointer_head_score: mix_logits must be [R, 1 + nmem]")
+    cs = [c.float().contiguous() for c in copies]
+    if any(c.dim() != 2 or c.shape[0] != R for c in cs):
+        raise ValueError("pointer_head_score: every copies[k] must be [R, len_k]")
+    targets = targets.reshape(R).contiguous()
+    n = len(cs)
+    ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
+    lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
+    prob = torch.empty(R, dtype=torch.float32, device=logits.device)
+    copy = torch.empty(R, dtype=torch.float32, device=logits.device)
+    A.call("case_pointer_head_score", _ptr(logits), _ptr(mix_logits), _ptr(keys), rows_per_source, C.cast(ptrs, C.c_void_p),
+           C.cast(lens, C.c_void_p), n, _ptr(targets), int(pad), _ptr(prob), _ptr(copy), R, V, keys.shape[1], _stream())
+    return prob, copy
+
+
 class BeamState(object):
     """The device-side state of one beam-search pass over B items x W slots and at most T steps: what K25 rewrites every step (``parent``,
     ``token``, ``cum``, ``len``, ``alive``), the [T, B, W] history K27 walks back, and the finished pool (best W retired hypotheses per item)."""
@@ -2104,6 +2147,15 @@ class SortedSource(object):
         """Every row ``width`` times in a row (the rows of one item's beam slots): the sorted keys are repeated, not sorted again."""
         out = object.__new__(SortedSource)
         out.ids, out.V, out.keys = self.ids.repeat_interleave(width, dim=0), self.V, self.keys.repeat_interleave(width, dim=0)
+        return out
+
+    def select(self, rows):
+        """The rows named by ``rows`` (a slice, or an int64 index tensor with repeats allowed): ids and sorted keys, not sorted again."""
+        out = object.__new__(SortedSource)
+        if isinstance(rows, slice):
+            out.ids, out.V, out.keys = self.ids[rows], self.V, self.keys[rows]
+        else:
+            out.ids, out.V, out.keys = self.ids.index_select(0, rows), self.V, self.keys.index_select(0, rows)
         return out
 
     @classmethod

@@ -72,7 +72,8 @@ enum {
   CASE_FEAT_ATTN_DECODE_APPEND = 1u << 16, /* case_attention_decode_append: the greedy step's cache append inside the attention launch */
   CASE_FEAT_LINEAR_SKINNY = 1u << 17,     /* case_linear_skinny */
   CASE_FEAT_BEAM_DECODE = 1u << 18,       /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
-  CASE_FEAT_SAMPLE_DECODE = 1u << 19      /* K28 case_pointer_head_sample */
+  CASE_FEAT_SAMPLE_DECODE = 1u << 19,     /* K28 case_pointer_head_sample */
+  CASE_FEAT_POINTER_SCORE = 1u << 20      /* K29 case_pointer_head_score */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -540,6 +541,19 @@ int case_pointer_head_sample(const float* logits, const float* mix_logits, const
                              const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k, float top_p, uint64_t seed,
                              uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
                              case_stream_t stream);
+/* K29 case_pointer_head_score (CASE_FEAT_POINTER_SCORE): the head of a teacher-forced scoring pass.  For row r with target y = targets[r]:
+ *   gen_y = exp(logits[r, y] - max) / sum_i exp(logits[r, i] - max);   pm = softmax(mix_logits[r, 0 .. nmem]);
+ *   ptr   = sum_k pm[1 + k] sum_{positions s of memory k whose source id is y} copies[k][r, s];
+ *   prob[r] = pm[0] gen_y + ptr;   copy[r] = ptr   (copy nullable).
+ * y == pad (pad >= 0; -1 = score every target) gives prob 1, copy 0: the position is not scored.  y outside [0, V) gives prob 0, copy 0.
+ * logits [R, V] f32, mix_logits [R, 1 + nmem] f32, targets [R] int64, copies / lens as in K23 with R rows (positions offset by the lengths
+ * before them, sum lens = S).  keys [R / rows_per_source, S]: row r reads key row r / rows_per_source -- the candidates of one item are
+ * consecutive rows and share its sorted keys unrepeated; R must be a multiple of rows_per_source.  One workgroup per row reads the logits
+ * once and keeps no vocabulary row: nmem <= 4, S <= 32768, V <= 131071 (the key format); CASE_E_UNSUPPORTED otherwise.  No atomics:
+ * two launches give the same bits. */
+int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                            const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad, float* prob,
+                            float* copy, int64_t R, int64_t V, int64_t S, case_stream_t stream);
 int case_pointer_attend_decode(const float* wq, const float* wq_add, const void* eu, const float* v, const void* value, const uint8_t* col_valid,
                                const uint8_t* row_valid, const float* prior, void* ctx, float* p, float* copy, int64_t B, int64_t S, int64_t H,
                                case_stream_t stream);
