@@ -44,44 +44,17 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
         dec_out = ops.layer_norm(x, self.norm1.weight, self.norm1.bias, self.norm1.eps)
         return dec_out, torch.cat([dec_in, dec_out, feat], dim=-1)
 
-    def _head(self, dec_in, x, ctxs, copies, feat, source_map):
-        dec_out, gen_in = self._head_parts(dec_in, x, feat)
-        gen = self._generate(gen_in, self.gen[1].p)
-        d1, d2 = self._mix(dec_out, ctxs, gen, copies, source_map)
-        return dec_out, gen, ((d1, d2) if self.training else ops.add(d1, d2))
+    train_returns_pair = True
 
-    def _step(self, dec_ids, mems, valid, weights, answer_rep, source_map, cache=None):
-        feat = self._feature(answer_rep, dec_ids.size(1))
-        dec_in, x, ctxs, copies = self._run_prefix(dec_ids, mems, valid, weights, feat, cache)
-        dec_out, gen, (d1, d2) = self._head(dec_in, x, ctxs, copies, feat, source_map)
-        return dec_out, gen, d1, d2
+    @property
+    def gen_dropout(self):
+        return self.gen[1].p
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
                 score_index=None):
-        B = source_map.size(0)
-        source_map = self._sorted(source_map)
-        mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
-        if score_index is not None:
-            return self._score(mems, valid, weights, source_map, BOS, score_index,
-                               feature_of=lambda T: self._feature(additional_decoder_feature, T))
-        if max_target_length is None:
-            max_target_length = groundtruth_index.size(1)
-        bos = self._bos(B, BOS, mems[0].device)
-        if self.training and groundtruth_index is not None:
-            dec_ids = torch.cat([bos, groundtruth_index[:, :-1]], dim=-1)
-            dec_out, gen, d1, d2 = self._step(dec_ids, mems, valid, weights, additional_decoder_feature, source_map)
-            return dec_out, gen, (d1, d2), groundtruth_index
-        if self.training:
-            return None
-        if beam_width:
-            return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width,
-                              feature_of=lambda T: self._feature(additional_decoder_feature, T))
-        if sampling:
-            return self._sample(mems, valid, weights, source_map, BOS, max_target_length, sampling,
-                                feature_of=lambda T: self._feature(additional_decoder_feature, T))
-        return self._greedy(mems, valid, weights, source_map, BOS, max_target_length,
-                            feature_of=lambda T: self._feature(additional_decoder_feature, T))
+        return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
+                         score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T))
 
 
 class RelevantPassageSelection(nn.Module):
@@ -224,12 +197,17 @@ class CaSE(nn.Module):
         dist1, dist2 = rg[2]
         return [loss_ps, loss_se, generation_nll(ops.add(dist1, dist2), data['response'])]
 
-    def do_test(self, data):
+    def _respond(self, data, **mode):
+        """Encode, select, extract, then the decoder in the mode the keyword names: (the decoder's raw result, rank)."""
         eq, ep, ps, se = self._encode_select_extract(data)
         rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
-                                             output=None, max_target_length=self.max_target_length)
-        return {'answer': rg[3], 'rank': ps[0]}
+                                             output=None, **mode)
+        return rg, ps[0]
+
+    def do_test(self, data):
+        rg, rank = self._respond(data, max_target_length=self.max_target_length)
+        return {'answer': rg[3], 'rank': rank}
 
     do_infer = do_test  # BASELINE.json's wording
 
@@ -237,12 +215,8 @@ class CaSE(nn.Module):
         """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``: ``width`` hypotheses per
         item ranked by length-normalised cost, retired on EOS): the ``do_test`` dict plus ``beam_score`` [B] (the answer's cum_cost / length),
         ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer)."""
-        eq, ep, ps, se = self._encode_select_extract(data)
-        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
-                                             encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
-                                             output=None, max_target_length=self.max_target_length,
-                                             beam_width=self.beam_width if width is None else width)
-        return {'answer': rg[3], 'rank': ps[0], 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width)
+        return {'answer': rg[3], 'rank': rank, 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
 
     def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None):
         """``do_test`` with every token DRAWN from the model's distribution (the reference's common/Generations.py ``sample`` loop; the draw is
@@ -255,11 +229,8 @@ class CaSE(nn.Module):
         handed up one layer, beyond the reference's interface: a caller with a stream of its own (antithetic or common random numbers across
         models, a replayed draw) supplies u of row b N + n at step t as uniforms[t, b N + n]; it replaces ``seed`` and the counter generator."""
         sampling = sampling_params(self.vocab2id, num_samples, temperature, top_k, top_p, seed, uniforms)
-        eq, ep, ps, se = self._encode_select_extract(data)
-        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
-                                             encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
-                                             output=None, max_target_length=self.max_target_length, sampling=sampling)
-        return {'answer': rg[3], 'rank': ps[0], 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling)
+        return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
     def do_score(self, data, answers=None):
         """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at
@@ -273,11 +244,8 @@ class CaSE(nn.Module):
         N = 1.  Under no_grad the head is K29 (no vocabulary row is built); with grad enabled the pass is differentiable."""
         if self.training:
             raise ValueError("do_score runs in eval mode: call model.eval() first")
-        eq, ep, ps, se = self._encode_select_extract(data)
-        out = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
-                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
-                                              output=None, score_index=data['response'] if answers is None else answers)
-        out['rank'] = ps[0]
+        out, rank = self._respond(data, score_index=data['response'] if answers is None else answers)
+        out['rank'] = rank
         return out
 
     def forward(self, data, method='mle_train'):

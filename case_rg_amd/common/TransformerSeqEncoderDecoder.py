@@ -22,7 +22,6 @@ from .TransformerDecoder import TransformerDecoder, TransformerDecoderLayer
 from .TransformerEncoder import TransformerEncoder, TransformerEncoderLayer
 from .Utils import generate_square_subsequent_mask
 
-_generate_square_subsequent_mask = generate_square_subsequent_mask
 MERGED_ENCODE = os.environ.get("CASE_MERGED_ENCODE", "1") != "0"  # A/B switch of TransformerSeqEncoder.forward_many
 QUERY_SPLIT = os.environ.get("CASE_QUERY_SPLIT", "1") != "0"  # A/B switch: the greedy step projects x_t alone for the additive-attention query
 
@@ -111,8 +110,166 @@ def sampling_params(vocab2id, num_samples=1, temperature=1.0, top_k=0, top_p=1.0
                 eos=vocab2id[EOS_WORD], unk=vocab2id[UNK_WORD], pad=vocab2id[PAD_WORD])
 
 
+class _DecodeMode:
+    """What differs between the decoding modes of ``PointerDecoderCore._decode``: how a step's head becomes the next ids [R, 1]
+    (``fused_step`` from the f32 logits, mixing logits, sorted source map and copy weights [R, len_k]; ``unfused_step`` from the unfused
+    ``gen`` / ``dist``), what happens between two steps, when the pass may end early and what it returns.  The rows of one item are
+    consecutive: row b * N + n is candidate n (beam slot, sample) of item b."""
+    counter = None  # the decoder attribute that receives the number of steps the pass ran: last_greedy_steps / last_beam_steps / last_sample_steps
+
+    def start(self, capturing, self_kvs, hist_valid):
+        pass
+
+    def after_step(self, t, self_kvs, hist_valid):
+        """Between step ``t`` and step t + 1 (not after the last step): -> the self-attention caches and prefix validity of step t + 1."""
+        return self_kvs, hist_valid
+
+
+class _GreedyMode(_DecodeMode):
+    """Argmax of the newest position with the lowest index on ties (the reference's CaSE/Model.py:94-123): K23, or ``row_argmax`` on the
+    unfused distribution.  With the decoder's ``eos_id`` set (the EOS-aware early stop) a finished answer is continued with PAD
+    (to_sentence stops at EOS anyway) and the pass may end once EVERY answer of the batch has produced EOS; None is the reference's
+    behaviour, always max_target_length steps (CaSE/Model.py:94).  K23 writes gen / dist back for the LAST step only (what the caller
+    gets): on step T - 1, or on any step when the early stop is armed and the stream is not capturing -- then any step may turn out to be
+    the last one.  -> (dec_out, gen, dist of the last step, answer [B, T], PAD behind a short pass)."""
+    counter = "last_greedy_steps"
+
+    def __init__(self, decoder, B, T, dev):
+        self.T, self.V, self.eos = T, decoder.tgt_vocab_size, decoder.eos_id
+        self.finished = None if self.eos is None else torch.zeros(B, dtype=torch.bool, device=dev)
+        self.picked, self.gen, self.dist = [], None, None
+
+    def start(self, capturing, self_kvs, hist_valid):
+        self.any_step_may_be_last = self.finished is not None and not capturing
+
+    def fused_step(self, t, logits, mix_logits, source_map, copies):
+        want = t == self.T - 1 or self.any_step_may_be_last
+        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want)
+        self.gen, self.dist = (gen.view(-1, 1, self.V), dist.view(-1, 1, self.V)) if want else (None, None)
+        return self._emit(ids.unsqueeze(1))
+
+    def unfused_step(self, t, gen, dist):
+        self.gen, self.dist = gen, dist
+        return self._emit(ops.row_argmax(dist[:, -1])[0].unsqueeze(1))
+
+    def _emit(self, ids):
+        if self.finished is not None:
+            ids = ids.masked_fill(self.finished.unsqueeze(1), 0)
+            self.finished = self.finished | ids[:, 0].eq(self.eos)
+        self.picked.append(ids)
+        return ids
+
+    def all_finished(self):
+        return self.finished is not None and bool(self.finished.all())
+
+    def result(self, dec_out):
+        answer = torch.cat(self.picked, dim=-1)
+        if answer.size(1) < self.T:
+            answer = torch.nn.functional.pad(answer, (0, self.T - answer.size(1)))
+        return dec_out, self.gen, self.dist, answer
+
+
+class _BeamMode(_DecodeMode):
+    """Beam search (the reference's common/Generations.py:112-190, per item on the device).  The W slots of an item are the rows
+    b * W + w, and every step is the greedy step on B * W rows followed by K24 (top-W of the mixed distribution; ``torch.topk`` on the
+    unfused one), K25 (the per-item merge, EOS / last-step retirement), K26 and, after the last step, K27 (the back-track).  K26 reorders
+    the self-attention caches by the chosen parents; a gather cannot run in place, so it writes into a second set of buffers and the two
+    sets swap roles every step.  A hypothesis retires on the decoder's ``beam_eos_id`` or at max_target_length; the pass may end once no
+    slot is alive.  -> (dec_out of the last step's rows, None, None, answer [B, T], beam_answers [B, W, T], beam_scores [B, W])."""
+    counter = "last_beam_steps"
+
+    def __init__(self, decoder, B, W, T, dev):
+        self.W, self.eos = W, decoder.beam_eos_id
+        self.state = ops.BeamState(B, W, T, dev)
+
+    def start(self, capturing, self_kvs, hist_valid):
+        spare = [[torch.zeros_like(c) for c in layers] for layers in self_kvs]
+        self.live = (self_kvs, hist_valid, [c for layers in self_kvs for c in layers])
+        self.spare = (spare, torch.zeros_like(hist_valid), [c for layers in spare for c in layers])
+
+    def fused_step(self, t, logits, mix_logits, source_map, copies):
+        _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W)
+        return self._advance(t, cand_p, cand_id)
+
+    def unfused_step(self, t, gen, dist):
+        return self._advance(t, *torch.topk(dist[:, -1].detach().float(), self.W, dim=-1))
+
+    def _advance(self, t, cand_p, cand_id):
+        ops.beam_advance(self.state, cand_p, cand_id, t, self.eos)
+        return self.state.token.view(-1, 1)
+
+    def after_step(self, t, self_kvs, hist_valid):
+        ops.beam_gather(self.live[2], self.spare[2], self.state.parent, t, self.live[1], self.spare[1])
+        self.live, self.spare = self.spare, self.live
+        return self.live[:2]
+
+    def all_finished(self):
+        return not bool(self.state.alive.any())
+
+    def result(self, dec_out):
+        return (dec_out, None, None) + ops.beam_backtrack(self.state)
+
+
+class _SampleMode(_DecodeMode):
+    """Sampled decoding (the reference's common/Generations.py:7-63 ``sample``, with the draw on the device).  The ``num_samples`` draws of
+    an item are the rows b * N + n.  K28 (ops.pointer_head_sample) takes K23's place: one launch draws the token of every row after
+    temperature / top-k / top-p, applies the loop's conventions (UNK for EOS at step 0, EOS forced at the last step, PAD behind the end)
+    and keeps the ``ended`` flags on the device; nothing is read back inside a step.  The unfused distribution feeds the same kernel
+    (``dist_in``).
+
+    ``params``: dict(num_samples, temperature, top_k, top_p, eos, unk, pad, seed, uniforms).  ``uniforms`` f32 [T, B * N] overrides the
+    RNG.  Otherwise row r of step t draws at counter rng_base + offset + r: with ``seed`` None, (seed, offset, state) is
+    ``config.next_rng(B * N)``, taken once per step in step order -- the global counter stream, so with a device step state installed a
+    captured pass draws NEW samples on every replay whose ``CaseStepState.rng_base`` has moved, and WITHOUT a device state a replay
+    repeats its samples (seed and offsets are frozen into the graph); with an integer ``seed`` the pass is private and reproducible:
+    (seed, offset t * B * N, no state).  A short pass is padded with PAD ids of probability 1.
+    -> (dec_out of the last step's rows, None, None, answer [B, T], samples [B, N, T], sample_probs [B, N, T], sample_scores [B, N])."""
+    counter = "last_sample_steps"
+
+    def __init__(self, B, T, dev, params):
+        self.B, self.N, self.T, self.R, self.pad = B, int(params["num_samples"]), T, B * int(params["num_samples"]), params["pad"]
+        self.seed, self.uniforms = params.get("seed"), params.get("uniforms")
+        if self.uniforms is not None and tuple(self.uniforms.shape) != (T, self.R):
+            raise ValueError("sampled decoding: uniforms must be [max_target_length, batch * num_samples] = [%d, %d]" % (T, self.R))
+        self.draw = (params["eos"], params["unk"], params["pad"], params["temperature"], params["top_k"], params["top_p"])
+        self.ended = torch.zeros(self.R, dtype=torch.uint8, device=dev)
+        self.picked, self.probs = [], []
+
+    def _draw(self, t, *head, **kw):
+        u = None if self.uniforms is None else self.uniforms[t]
+        rng = None if u is not None else config.next_rng(self.R) if self.seed is None else (int(self.seed), t * self.R, None)
+        _, _, tok, p = ops.pointer_head_sample(*head, self.ended, t == 0, t == self.T - 1, *self.draw, rng=rng, uniforms=u, **kw)
+        self.picked.append(tok.unsqueeze(1))
+        self.probs.append(p.unsqueeze(1))
+        return self.picked[-1]
+
+    def fused_step(self, t, logits, mix_logits, source_map, copies):
+        return self._draw(t, logits, mix_logits, source_map, copies)
+
+    def unfused_step(self, t, gen, dist):
+        return self._draw(t, None, None, None, None, dist_in=dist[:, -1].detach().float())
+
+    def all_finished(self):
+        return bool(self.ended.all())
+
+    def result(self, dec_out):
+        B, N, T = self.B, self.N, self.T
+        samples, sample_probs = torch.cat(self.picked, dim=1), torch.cat(self.probs, dim=1)
+        if samples.size(1) < T:  # every row had ended: PAD, probability 1
+            samples = torch.nn.functional.pad(samples, (0, T - samples.size(1)))
+            sample_probs = torch.nn.functional.pad(sample_probs, (0, T - sample_probs.size(1)), value=1.0)
+        emitted = samples.ne(self.pad)
+        nll = -torch.log(sample_probs.clamp_min(1e-30)) * emitted
+        sample_scores = nll.sum(dim=1) / emitted.sum(dim=1).clamp_min(1)
+        samples = samples.view(B, N, T)
+        return dec_out, None, None, samples[:, 0].contiguous(), samples, sample_probs.view(B, N, T), sample_scores.view(B, N)
+
+
 class PointerDecoderCore(nn.Module):
-    """Shared machinery of the three pointer-generator decoders."""
+    """Shared machinery of the three pointer-generator decoders: the dispatch of their ``forward``s (``_run``), the teacher-forced and the
+    KV-cached passes and the heads.  A decoder adds its modules, ``_head_parts`` and the two settings below."""
+    gen_dropout = 0.0  # dropout between the generator's two Linears (training)
+    train_returns_pair = False  # the training branch returns (dist1, dist2) instead of their sum
 
     def _build(self, num_memories, num_layers, nhead, vocab, H, query_width, emb_matrix=None, max_len=1000):
         self.tgt_vocab_size, self.num_layers, self.hidden_size = vocab, num_layers, H
@@ -135,13 +292,6 @@ class PointerDecoderCore(nn.Module):
         self.score_chunk_rows = 2048
 
     # ------------------------------------------------------------------------------------------
-    def _prepare(self, encode_memories, encode_masks, encode_weights, batch_size):
-        H = self.hidden_size
-        mems = [m.reshape(batch_size, -1, H) for m in encode_memories]
-        valid = [m.reshape(batch_size, -1).contiguous() for m in encode_masks]
-        weights = None if encode_weights is None else [w.reshape(batch_size, -1) for w in encode_weights]
-        return mems, valid, weights
-
     def _sorted(self, source_map):
         """The batch's source map with its (token, position) keys sorted on the device, once per forward: every
         pointer scatter of the batch -- one per training step, one per generated token -- then adds run by run without atomics."""
@@ -158,19 +308,16 @@ class PointerDecoderCore(nn.Module):
                             eu=self.attns[i].project_keys_exp(m) if fused else None))
         return out
 
-    def _run_prefix(self, dec_ids, mems, valid, weights, feature, cache=None):
+    def _run_prefix(self, dec_ids, mems, valid, weights, feature):
         """decs[0] -> attns[0] -> decs[1] -> attns[1] (a sequential chain, CaSE/Model.py:74-83)."""
         dec_in = _embed(self.embedding, dec_ids, self.training)
         tgt_valid = dec_ids.ne(0)
         x = dec_in
         ctxs, copies = [], []
         for i, mem in enumerate(mems):
-            c = None if cache is None else cache[i]
-            x = self.decs[i].forward_batch_first(x, mem, tgt_valid, valid[i], causal=True,
-                                                 memory_kvs=None if c is None else c["kvs"])
+            x = self.decs[i].forward_batch_first(x, mem, tgt_valid, valid[i], causal=True)
             q = x if feature is None else torch.cat([x, feature], dim=-1)
-            ctx, p = self.attns[i].attend(q, mem, mem, row_valid=tgt_valid, col_valid=valid[i],
-                                          uh=None if c is None else c["uh"])
+            ctx, p = self.attns[i].attend(q, mem, mem, row_valid=tgt_valid, col_valid=valid[i])
             ctxs.append(ctx)
             if weights is not None:
                 p = weights[i].unsqueeze(1) * p
@@ -178,9 +325,13 @@ class PointerDecoderCore(nn.Module):
             copies.append(p)
         return dec_in, x, ctxs, copies
 
+    def _check_length(self, T):
+        if T > self.embedding[1].pe.size(0):
+            raise RuntimeError("max_target_length %d exceeds max_len %d" % (T, self.embedding[1].pe.size(0)))
+
     def _cache_setup(self, mems, max_target_length, feat):
-        """What a cached decoding pass (greedy or beam) builds once: the step-invariant memory projections, one empty self-attention cache
-        per layer, the prefix validity and the step-invariant halves of the additive-attention queries."""
+        """What a cached decoding pass builds once: the step-invariant memory projections, one empty self-attention cache per layer, the
+        prefix validity and the step-invariant halves of the additive-attention queries."""
         B, dev = mems[0].shape[0], mems[0].device
         # the raw-pointer decode kernels (K21 / K22 / K23) have no autograd Function behind them: eval mode AND no_grad (the reference only
         # predicts under no_grad; a caller that differentiates an eval-mode greedy pass keeps the differentiable launches)
@@ -188,8 +339,7 @@ class PointerDecoderCore(nn.Module):
         cache = self._memory_cache(mems, absorb=inference)
         self_kvs = [dec.new_self_cache(B, max_target_length, mems[0]) for dec in self.decs]
         hist_valid = torch.zeros(B, max_target_length, dtype=torch.bool, device=dev)
-        if max_target_length > self.embedding[1].pe.size(0):
-            raise RuntimeError("max_target_length %d exceeds max_len %d" % (max_target_length, self.embedding[1].pe.size(0)))
+        self._check_length(max_target_length)
         # the feature half of the additive-attention query does not change over the steps: projected once per pass (BilinearAttention.split_query)
         splits = [self.attns[i].split_query(feat, self.hidden_size) if (QUERY_SPLIT and inference and feat is not None and cache[i]["eu"] is not None) else None
                   for i in range(len(mems))]
@@ -218,167 +368,57 @@ class PointerDecoderCore(nn.Module):
             copies.append(p)
         return dec_in, x, ctxs, copies
 
-    def _greedy(self, mems, valid, weights, source_map, BOS, max_target_length, feature_of=None):
-        """KV-cached greedy decoding (K13).  Step semantics are the reference's (CaSE/Model.py:94-123): fixed number of steps,
-        argmax of the newest position with the lowest index on ties, PAD tokens in the prefix masked as keys -- but each step
-        computes ONE new position: self-attention K/V of earlier positions, the per-layer K/V projections of both memories and
-        the additive-attention keys are cached, so a step streams the caches once instead of recomputing the prefix
-        (O(T) instead of O(T^2) decoder work, no per-step projection of the 3840-token passage memory)."""
-        B, dev = mems[0].shape[0], mems[0].device
-        feat = None if feature_of is None else feature_of(1)
-        inference, cache, self_kvs, hist_valid, splits = self._cache_setup(mems, max_target_length, feat)
-        ids = self._bos(B, BOS, dev)
-        picked = []
-        finished = None if self.eos_id is None else torch.zeros(B, dtype=torch.bool, device=dev)
-        capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
-        fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, self.tgt_vocab_size, len(mems)))
-        for t in range(max_target_length):
-            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid)
-            if fused_head:  # K23: vocabulary softmax, mixing, pointer scatter and argmax in one launch
-                dec_out, gen_in = self._head_parts(dec_in, x, feat)
-                # the distributions leave the device for the LAST step only (what the caller gets back); with an EOS-aware early stop any
-                # step may turn out to be the last one
-                want = t == max_target_length - 1 or (finished is not None and not capturing)
-                gen, dist, ids = self._head_decode(dec_out, gen_in, ctxs, copies, source_map, want)
-            else:
-                dec_out, gen, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
-                ids = ops.row_argmax(dist[:, -1])[0].unsqueeze(1)
-            if finished is not None:
-                ids = ids.masked_fill(finished.unsqueeze(1), 0)  # PAD behind a finished answer (to_sentence stops at EOS anyway)
-                finished = finished | ids[:, 0].eq(self.eos_id)
-            picked.append(ids)
-            if (finished is not None and not capturing and (t + 1) % self.eos_check_every == 0 and t + 1 < max_target_length
-                    and bool(finished.all())):
-                break
-        self.last_greedy_steps = len(picked)
-        answer = torch.cat(picked, dim=-1)
-        if answer.size(1) < max_target_length:
-            answer = torch.nn.functional.pad(answer, (0, max_target_length - answer.size(1)))
-        return dec_out, gen, dist, answer
+    @staticmethod
+    def _per_item(n, mems, valid, weights, source_map, feat, keys=True, unit_too=False):
+        """Every item's row ``n`` times in a row (row b * n + k): the memories, masks, copy priors, the feature and the source map of a pass
+        whose candidates (beam slots, samples, answers to score) are extra batch rows, so a pass costs n x the memory footprint per item.
+        A SortedSource repeats its sorted keys, it does not sort again; ``keys=False`` leaves the source map as it is (K29 reads key row
+        r // rows_per_source).  n = 1 launches nothing unless ``unit_too`` (beam search at width 1 repeats)."""
+        if n == 1 and not unit_too:
+            return mems, valid, weights, source_map, feat
+        mems = [m.repeat_interleave(n, dim=0) for m in mems]
+        valid = [v.repeat_interleave(n, dim=0) for v in valid]
+        weights = None if weights is None else [w.repeat_interleave(n, dim=0) for w in weights]
+        if keys:
+            source_map = source_map.expand(n) if isinstance(source_map, ops.SortedSource) else source_map.repeat_interleave(n, dim=0)
+        return mems, valid, weights, source_map, None if feat is None else feat.repeat_interleave(n, dim=0)
 
-    def _beam(self, mems, valid, weights, source_map, BOS, max_target_length, width, feature_of=None):
-        """Beam search over the cached step (the reference's common/Generations.py:112-190, per item on the device).  The slots of an item
-        are extra batch rows (row b * W + w): memories, masks, copy priors, the e^{2 uh} caches and the sorted source keys are repeated W
-        times once per pass, and every step is ``_greedy``'s step on B * W rows followed by K24 (top-W of the mixed distribution), K25
-        (the per-item merge, EOS / last-step retirement), K26 (the self-attention caches reordered by the chosen parents into a second
-        set of buffers) and, after the last step, K27 (the back-track).  A hypothesis retires on ``beam_eos_id`` or at ``max_target_length``.
-        -> (dec_out of the last step's rows, None, None, answer [B, T], beam_answers [B, W, T], beam_scores [B, W])."""
-        B, dev, W, T = mems[0].shape[0], mems[0].device, int(width), max_target_length
-        if not ops.beam_supported(W):
-            raise RuntimeError("beam search: width %d is outside what the beam kernels are built for (1 .. 8)" % W)
-        mems = [m.repeat_interleave(W, dim=0) for m in mems]
-        valid = [v.repeat_interleave(W, dim=0) for v in valid]
-        weights = None if weights is None else [w.repeat_interleave(W, dim=0) for w in weights]
-        if isinstance(source_map, ops.SortedSource):
-            source_map = source_map.expand(W)
-        else:
-            source_map = source_map.repeat_interleave(W, dim=0)
-        feat = None if feature_of is None else feature_of(1).repeat_interleave(W, dim=0)
-        inference, cache, kv_a, valid_a, splits = self._cache_setup(mems, T, feat)
-        kv_b = [[torch.zeros_like(c) for c in layers] for layers in kv_a]  # K26's destination: the two sets swap roles every step
-        valid_b = torch.zeros_like(valid_a)
-        flat_a, flat_b = [c for layers in kv_a for c in layers], [c for layers in kv_b for c in layers]
-        state = ops.BeamState(B, W, T, dev)
-        ids = self._bos(B * W, BOS, dev)
-        capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
-        fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, self.tgt_vocab_size, len(mems)))
-        steps = 0
+    def _decode(self, mode, mems, valid, weights, source_map, feat, BOS, max_target_length):
+        """The KV-cached decoding pass (K13) every mode shares.  Step semantics are the reference's (CaSE/Model.py:94-123): a fixed number
+        of steps, PAD tokens in the prefix masked as keys -- but each step computes ONE new position: self-attention K/V of earlier
+        positions, the per-layer K/V projections of both memories and the additive-attention keys are cached, so a step streams the caches
+        once instead of recomputing the prefix (O(T) instead of O(T^2) decoder work, no per-step projection of the 3840-token passage
+        memory).  ``mode`` (a ``_DecodeMode``) turns a step's head into the next ids and owns everything else that differs between greedy,
+        beam and sampled decoding.  A pass ends early once ``mode.all_finished()``, read every ``eos_check_every`` steps: one host sync per
+        8 tokens, none per token, and none at all in a captured pass, which cannot branch on device data and runs its fixed T steps."""
+        R, dev, T = mems[0].shape[0], mems[0].device, max_target_length
+        inference, cache, self_kvs, hist_valid, splits = self._cache_setup(mems, T, feat)
+        ids = self._bos(R, BOS, dev)
+        capturing = torch.cuda.is_current_stream_capturing()
+        fused_head = inference and ops.pointer_head_supported(source_map, self.tgt_vocab_size, len(mems))
+        mode.start(capturing, self_kvs, hist_valid)
         for t in range(T):
-            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, kv_a, valid_a)
-            if fused_head:  # K24: vocabulary softmax, mixing, pointer scatter and the W best entries in one launch
+            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid)
+            if fused_head:  # vocabulary softmax, mixing, pointer scatter and the mode's choice in one launch
                 dec_out, gen_in = self._head_parts(dec_in, x, feat)
                 logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
-                _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, [c.reshape(B * W, -1) for c in copies], W)
-            else:  # no K23 for this pass (or a differentiated one): the unfused distribution and torch.topk feed the same beam kernels
-                dec_out, _, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
-                cand_p, cand_id = torch.topk(dist[:, -1].detach().float(), W, dim=-1)
-            ops.beam_advance(state, cand_p, cand_id, t, self.beam_eos_id)
-            ids = state.token.view(B * W, 1)
+                ids = mode.fused_step(t, logits, mix_logits, source_map, [c.reshape(R, -1) for c in copies])
+            else:  # no fused head for this pass (or a differentiated one): the unfused distribution feeds the mode
+                dec_out, gen, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
+                ids = mode.unfused_step(t, gen, dist)
             steps = t + 1
             if steps == T:
                 break
-            ops.beam_gather(flat_a, flat_b, state.parent, t, valid_a, valid_b)
-            kv_a, kv_b, flat_a, flat_b, valid_a, valid_b = kv_b, kv_a, flat_b, flat_a, valid_b, valid_a
-            if not capturing and steps % self.eos_check_every == 0 and not bool(state.alive.any()):
+            self_kvs, hist_valid = mode.after_step(t, self_kvs, hist_valid)
+            if not capturing and steps % self.eos_check_every == 0 and mode.all_finished():
                 break
-        self.last_beam_steps = steps
-        answer, beam_answers, beam_scores = ops.beam_backtrack(state)
-        return dec_out, None, None, answer, beam_answers, beam_scores
-
-    def _sample(self, mems, valid, weights, source_map, BOS, max_target_length, params, feature_of=None):
-        """Sampled decoding over the cached step (the reference's common/Generations.py:7-63 ``sample``, with the draw on the device).  The
-        ``num_samples`` draws of an item are extra batch rows (row b * N + n), built like ``_beam``'s slots: memories, masks, copy priors, the
-        e^{2 uh} caches and the sorted source keys are repeated N times once per pass (N x the memory footprint per item).  Every step is
-        ``_greedy``'s step on B * N rows with K28 (ops.pointer_head_sample) in place of K23: one launch draws the token of every row after
-        temperature / top-k / top-p, applies the loop's conventions (UNK for EOS at step 0, EOS forced at the last step, PAD behind the end)
-        and keeps the ``ended`` flags on the device; nothing is read back inside a step.  When the fused head is not eligible the unfused
-        distribution feeds the same kernel (``dist_in``).
-
-        ``params``: dict(num_samples, temperature, top_k, top_p, eos, unk, pad, seed, uniforms).  ``uniforms`` f32 [T, B * N] overrides the
-        RNG.  Otherwise row r of step t draws at counter rng_base + offset + r: with ``seed`` None, (seed, offset, state) is
-        ``config.next_rng(B * N)`` per step -- the global counter stream, so with a device step state installed a captured pass draws NEW
-        samples on every replay whose ``CaseStepState.rng_base`` has moved, and WITHOUT a device state a replay repeats its samples (seed and
-        offsets are frozen into the graph); with an integer ``seed`` the pass is private and reproducible: (seed, offset t * B * N, no state).
-        -> (dec_out of the last step's rows, None, None, answer [B, T], samples [B, N, T], sample_probs [B, N, T], sample_scores [B, N])."""
-        B, dev, N, T = mems[0].shape[0], mems[0].device, int(params["num_samples"]), max_target_length
-        V = self.tgt_vocab_size
-        if not ops.sample_supported(V):
-            raise RuntimeError("sampled decoding: the vocabulary (%d) is beyond what the sampling kernel holds in LDS (V <= 36000)" % V)
-        if N > 1:
-            mems = [m.repeat_interleave(N, dim=0) for m in mems]
-            valid = [v.repeat_interleave(N, dim=0) for v in valid]
-            weights = None if weights is None else [w.repeat_interleave(N, dim=0) for w in weights]
-            source_map = source_map.expand(N) if isinstance(source_map, ops.SortedSource) else source_map.repeat_interleave(N, dim=0)
-        feat = None if feature_of is None else feature_of(1)
-        if feat is not None and N > 1:
-            feat = feat.repeat_interleave(N, dim=0)
-        R = B * N
-        inference, cache, self_kvs, hist_valid, splits = self._cache_setup(mems, T, feat)
-        ids = self._bos(R, BOS, dev)
-        ended = torch.zeros(R, dtype=torch.uint8, device=dev)
-        capturing = torch.cuda.is_current_stream_capturing()  # a captured pass cannot branch on device data: fixed T steps
-        fused_head = (inference and hasattr(self, "_head_parts") and ops.pointer_head_supported(source_map, V, len(mems)))
-        seed, uniforms = params.get("seed"), params.get("uniforms")
-        if uniforms is not None and tuple(uniforms.shape) != (T, R):
-            raise ValueError("sampled decoding: uniforms must be [max_target_length, batch * num_samples] = [%d, %d]" % (T, R))
-        draw = (params["eos"], params["unk"], params["pad"], params["temperature"], params["top_k"], params["top_p"])
-        picked, probs = [], []
-        for t in range(T):
-            dec_in, x, ctxs, copies = self._cached_layers(t, ids, mems, valid, weights, feat, cache, splits, self_kvs, hist_valid)
-            if uniforms is not None:
-                rng, u = None, uniforms[t]
-            else:
-                rng, u = (config.next_rng(R) if seed is None else (int(seed), t * R, None)), None
-            if fused_head:  # K28: vocabulary softmax, mixing, pointer scatter and the draw in one launch
-                dec_out, gen_in = self._head_parts(dec_in, x, feat)
-                logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
-                _, _, tok, p = ops.pointer_head_sample(logits, mix_logits, source_map, [c.reshape(R, -1) for c in copies], ended, t == 0, t == T - 1,
-                                                       *draw, rng=rng, uniforms=u)
-            else:  # no K23 for this pass: the unfused distribution feeds the same draw
-                dec_out, _, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
-                _, _, tok, p = ops.pointer_head_sample(None, None, None, None, ended, t == 0, t == T - 1, *draw, rng=rng, uniforms=u,
-                                                       dist_in=dist[:, -1].detach().float())
-            ids = tok.unsqueeze(1)
-            picked.append(ids)
-            probs.append(p.unsqueeze(1))
-            if not capturing and (t + 1) % self.eos_check_every == 0 and t + 1 < T and bool(ended.all()):
-                break
-        self.last_sample_steps = len(picked)
-        samples, sample_probs = torch.cat(picked, dim=1), torch.cat(probs, dim=1)
-        if samples.size(1) < T:  # every row had ended: PAD, probability 1
-            samples = torch.nn.functional.pad(samples, (0, T - samples.size(1)))
-            sample_probs = torch.nn.functional.pad(sample_probs, (0, T - sample_probs.size(1)), value=1.0)
-        emitted = samples.ne(params["pad"])
-        nll = -torch.log(sample_probs.clamp_min(1e-30)) * emitted
-        sample_scores = nll.sum(dim=1) / emitted.sum(dim=1).clamp_min(1)
-        samples = samples.view(B, N, T)
-        return dec_out, None, None, samples[:, 0].contiguous(), samples, sample_probs.view(B, N, T), sample_scores.view(B, N)
+        setattr(self, mode.counter, steps)
+        return mode.result(dec_out)
 
     def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None):
         """Teacher-forced scoring of given answers (eval mode): ``answers`` int64 [B, T'] or [B, N, T'], ``pad`` marking the positions that
         are not scored.  One full-prefix pass over dec_ids = cat[BOS, answers[:, :-1]] (``_run_prefix``, causal), then the head over row
-        chunks of at most ``score_chunk_rows`` (candidate, position) rows.  The N candidates of an item are extra batch rows (row b * N + n),
-        built like ``_beam``'s slots: memories, masks and copy priors are repeated N times, so a pass costs N x the memory footprint per item.
+        chunks of at most ``score_chunk_rows`` (candidate, position) rows.  The N candidates of an item are extra batch rows (``_per_item``).
         The sorted source keys are NOT repeated: the rows of an item are consecutive and K29 reads key row r // rows_per_source.
         Under no_grad (and unless CASE_POINTER_SCORE=off) a chunk's head is ``_head_logits`` + K29 (ops.pointer_head_score): one read of the
         logits, no [rows, V] distribution.  With grad enabled it is the unfused differentiable chain of the training branch (``_generate``,
@@ -393,15 +433,9 @@ class PointerDecoderCore(nn.Module):
             raise ValueError("scoring: answers must be int64 [B, T] or [B, N, T] with the batch's B")
         B, N, T = answers.shape
         dev, V, H = mems[0].device, self.tgt_vocab_size, self.hidden_size
-        if T > self.embedding[1].pe.size(0):
-            raise RuntimeError("max_target_length %d exceeds max_len %d" % (T, self.embedding[1].pe.size(0)))
-        if N > 1:
-            mems = [m.repeat_interleave(N, dim=0) for m in mems]
-            valid = [v.repeat_interleave(N, dim=0) for v in valid]
-            weights = None if weights is None else [w.repeat_interleave(N, dim=0) for w in weights]
+        self._check_length(T)
         feat = None if feature_of is None else feature_of(T)
-        if feat is not None and N > 1:
-            feat = feat.repeat_interleave(N, dim=0)
+        mems, valid, weights, source_map, feat = self._per_item(N, mems, valid, weights, source_map, feat, keys=False)
         R = B * N
         tgt = answers.reshape(R, T).to(dev)
         dec_ids = torch.cat([self._bos(R, BOS, dev), tgt[:, :-1]], dim=-1)
@@ -451,8 +485,43 @@ class PointerDecoderCore(nn.Module):
         loss = ((-torch.log(p + 1e-8) * scored).sum() / count.clamp_min(1)).reshape(1)
         return dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
 
+    def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
+             score_index, feature_of=None):
+        """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
+        (CaSE's answer representation), or None."""
+        B, dev = source_map.size(0), encode_memories[0].device
+        source_map = self._sorted(source_map)
+        mems = [m.reshape(B, -1, self.hidden_size) for m in encode_memories]
+        valid = [m.reshape(B, -1).contiguous() for m in encode_masks]
+        weights = None if encode_weights is None else [w.reshape(B, -1) for w in encode_weights]
+        if score_index is not None:
+            return self._score(mems, valid, weights, source_map, BOS, score_index, feature_of=feature_of)
+        T = groundtruth_index.size(1) if max_target_length is None else max_target_length
+        if self.training and groundtruth_index is not None:
+            dec_ids = torch.cat([self._bos(B, BOS, dev), groundtruth_index[:, :-1]], dim=-1)
+            feat = None if feature_of is None else feature_of(dec_ids.size(1))
+            dec_out, gen, dist = self._head(*self._run_prefix(dec_ids, mems, valid, weights, feat), feat, source_map)
+            return dec_out, gen, dist, groundtruth_index
+        if self.training:
+            return None
+        feat = None if feature_of is None else feature_of(1)
+        if beam_width:
+            W = int(beam_width)
+            if not ops.beam_supported(W):
+                raise RuntimeError("beam search: width %d is outside what the beam kernels are built for (1 .. 8)" % W)
+            mode, n = _BeamMode(self, B, W, T, dev), W
+        elif sampling:
+            if not ops.sample_supported(self.tgt_vocab_size):
+                raise RuntimeError("sampled decoding: the vocabulary (%d) is beyond what the sampling kernel holds in LDS (V <= 36000)"
+                                   % self.tgt_vocab_size)
+            mode, n = _SampleMode(B, T, dev, sampling), int(sampling["num_samples"])
+        else:
+            mode, n = _GreedyMode(self, B, T, dev), 1
+        # beam search repeats its rows at width 1 too
+        return self._decode(mode, *self._per_item(n, mems, valid, weights, source_map, feat, unit_too=bool(beam_width)), BOS, T)
+
     def _head_logits(self, dec_out, gen_in, ctxs):
-        """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 take."""
+        """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 / K28 / K29 take."""
         B, V = dec_out.shape[0], self.tgt_vocab_size
         h = ops.linear(gen_in, self.gen[0].weight, self.gen[0].bias)
         logits = ops.linear(h, self.gen[-2].weight, None, out_dtype=torch.float32)
@@ -463,16 +532,12 @@ class PointerDecoderCore(nn.Module):
             mix_logits = ops.linear(torch.cat(parts, dim=-1), self.mix.weight, self.mix.bias, out_dtype=torch.float32)
         return logits.reshape(B, V), mix_logits.reshape(B, -1)
 
-    def _head_decode(self, dec_out, gen_in, ctxs, copies, source_map, want_dists=True):
-        """The head of one greedy step through K23 (ops.pointer_head_decode): the two generator Linears and the mixing Linear, then ONE
-        launch for softmax over V, softmax over the mixing logits, p0 x gen + the pointer scatter, and the argmax."""
-        B, V = dec_out.shape[0], self.tgt_vocab_size
-        logits, mix_logits = self._head_logits(dec_out, gen_in, ctxs)
-        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, [c.reshape(B, -1) for c in copies],
-                                                 want_gen=want_dists, want_dist=want_dists)
-        if not want_dists:
-            return None, None, ids.unsqueeze(1)
-        return gen.view(B, 1, V), dist.view(B, 1, V), ids.unsqueeze(1)
+    def _head(self, dec_in, x, ctxs, copies, feat, source_map):
+        """The unfused head: (dec_out, gen, dist)."""
+        dec_out, gen_in = self._head_parts(dec_in, x, feat)
+        gen = self._generate(gen_in, self.gen_dropout)
+        d1, d2 = self._mix(dec_out, ctxs, gen, copies, source_map)
+        return dec_out, gen, ((d1, d2) if self.training and self.train_returns_pair else ops.add(d1, d2))
 
     def _generate(self, gen_in, hidden_drop):
         """gen = softmax(W_v (drop(W_h x + b)))  -- f32 logits and probabilities (K10)."""
@@ -518,38 +583,9 @@ class TransformerSeqDecoder(PointerDecoderCore):
         dec_out = ops.layer_norm(x, self.norm.weight, self.norm.bias, self.norm.eps)
         return dec_out, torch.cat([dec_in, dec_out], dim=-1)
 
-    def _head(self, dec_in, x, ctxs, copies, feat, source_map):
-        dec_out, gen_in = self._head_parts(dec_in, x, feat)
-        gen = self._generate(gen_in, 0.0)
-        d1, d2 = self._mix(dec_out, ctxs, gen, copies, source_map)
-        return dec_out, gen, d1 + d2
-
-    def _step(self, dec_ids, mems, valid, weights, source_map, cache=None):
-        dec_in, x, ctxs, copies = self._run_prefix(dec_ids, mems, valid, weights, None, cache)
-        return self._head(dec_in, x, ctxs, copies, None, source_map)
-
-    def _source(self, source_maps):
-        return torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
-
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
-        source_map = self._source(source_maps) if isinstance(source_maps, (list, tuple)) else source_maps
-        B = source_map.size(0)
-        source_map = self._sorted(source_map)
-        mems, valid, weights = self._prepare(encode_memories, encode_masks, encode_weights, B)
-        if score_index is not None:
-            return self._score(mems, valid, weights, source_map, BOS, score_index)
-        if max_target_length is None:
-            max_target_length = groundtruth_index.size(1)
-        bos = self._bos(B, BOS, mems[0].device)
-        if self.training and groundtruth_index is not None:
-            dec_ids = torch.cat([bos, groundtruth_index[:, :-1]], dim=-1)
-            dec_out, gen, dist = self._step(dec_ids, mems, valid, weights, source_map)
-            return dec_out, gen, dist, groundtruth_index
-        if self.training:
-            return None
-        if beam_width:
-            return self._beam(mems, valid, weights, source_map, BOS, max_target_length, beam_width)
-        if sampling:
-            return self._sample(mems, valid, weights, source_map, BOS, max_target_length, sampling)
-        return self._greedy(mems, valid, weights, source_map, BOS, max_target_length)
+        if isinstance(source_maps, (list, tuple)):
+            source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
+        return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
+                         score_index)

@@ -1384,12 +1384,14 @@ extern "C" int case_pointer_attend_decode(const float* wq, const float* wq_add, 
   return case_check_launch("case_pointer_attend_decode");
 }
 
-static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
-                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S) {
-  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && B > 0 && V > 0 && S > 0 && nmem >= 1 && B < (1ll << 31), "%s: bad argument", who);
-  if (nmem > PH_MAX_MEM || V > 36000 || S > 32768)
-    return case_set_error(CASE_E_UNSUPPORTED, "%s: built for <= %d memories, V <= 36000, S <= 32768 (run the softmax / "
-                                              "scatter / argmax launches)", who, PH_MAX_MEM);
+// the operands K23 / K24 / K28 (HeadArgs) and K29 (ScoreArgs) share: logits, mixing logits, sorted keys and the copy weights of every memory,
+// whose lengths must add up to the source map's
+template <typename Args>
+static int pointer_head_fill(Args& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                             const int64_t* lens, int32_t nmem, int64_t R, int64_t V, int64_t S, int64_t max_v, const char* instead) {
+  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && R > 0 && V > 0 && S > 0 && nmem >= 1 && R < (1ll << 31), "%s: bad argument", who);
+  if (nmem > PH_MAX_MEM || V > max_v || S > 32768)
+    return case_set_error(CASE_E_UNSUPPORTED, "%s: built for <= %d memories, V <= %lld, S <= 32768%s", who, PH_MAX_MEM, (long long)max_v, instead);
   a.logits = logits;
   a.mix_logits = mix_logits;
   a.keys = keys;
@@ -1401,34 +1403,48 @@ static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, 
     CASE_REQUIRE(m >= nmem || (copies[m] && lens[m] > 0), "%s: null copy weights", who);
   }
   CASE_REQUIRE(total == S, "%s: the memories hold %lld positions, the source map %lld", who, (long long)total, (long long)S);
-  a.gen = gen;
-  a.dist = dist;
-  a.ids = nullptr;
-  a.top = nullptr;
   a.V = V;
   a.S = S;
   a.nmem = nmem;
   return CASE_OK;
 }
 
+constexpr int64_t PH_MAX_V = 36000, PS_MAX_V = 131071;  // the vocabulary row in LDS; the key format alone
+
+static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
+                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S) {
+  const int rc = pointer_head_fill(a, who, logits, mix_logits, keys, copies, lens, nmem, B, V, S, PH_MAX_V,
+                                   " (run the softmax / scatter / argmax launches)");
+  if (rc != CASE_OK) return rc;
+  a.gen = gen;
+  a.dist = dist;
+  a.ids = nullptr;
+  a.top = nullptr;
+  return CASE_OK;
+}
+
 static size_t pointer_head_lds(int64_t V) { return (size_t)(((V + 3) & ~(int64_t)3) + (PH_THREADS + 4) + PH_THREADS + 64) * 4; }
+
+// the dynamic-LDS ceiling of a kernel that keeps the vocabulary row in LDS, raised once per process (``done``: the caller's static flag)
+static int pointer_head_reserve(const void* kernel, bool& done, const char* who) {
+  if (!done && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess)
+    return case_set_error(CASE_E_LAUNCH, "%s: cannot reserve LDS", who);
+  done = true;
+  return CASE_OK;
+}
 
 extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                         const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
                                         int64_t S, case_stream_t stream) {
   CASE_REQUIRE(ids, "case_pointer_head_decode: bad argument");
   HeadArgs a;
-  const int rc = pointer_head_args(a, "case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
+  int rc = pointer_head_args(a, "case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
   if (rc != CASE_OK) return rc;
   a.ids = ids;
   a.top = top;
   static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_decode_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
-        hipSuccess)
-      return case_set_error(CASE_E_LAUNCH, "case_pointer_head_decode: cannot reserve LDS");
-    attr = true;
-  }
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel), attr, "case_pointer_head_decode");
+  if (rc != CASE_OK) return rc;
   hipLaunchKernelGGL(pointer_head_decode_kernel, dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a);
   return case_check_launch("case_pointer_head_decode");
 }
@@ -1439,15 +1455,11 @@ extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logi
   CASE_REQUIRE(cand_p && cand_id, "case_pointer_head_beam: bad argument");
   if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_beam: width %d outside 1 .. min(%d, V)", W, PH_MAX_W);
   HeadArgs a;
-  const int rc = pointer_head_args(a, "case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+  int rc = pointer_head_args(a, "case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
   if (rc != CASE_OK) return rc;
   static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_beam_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
-        hipSuccess)
-      return case_set_error(CASE_E_LAUNCH, "case_pointer_head_beam: cannot reserve LDS");
-    attr = true;
-  }
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel), attr, "case_pointer_head_beam");
+  if (rc != CASE_OK) return rc;
   hipLaunchKernelGGL(pointer_head_beam_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id, (int)W);
   return case_check_launch("case_pointer_head_beam");
 }
@@ -1466,7 +1478,7 @@ extern "C" int case_pointer_head_sample(const float* logits, const float* mix_lo
     const int rc = pointer_head_args(a, "case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
     if (rc != CASE_OK) return rc;
   } else {
-    if (V > 36000) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_sample: built for V <= 36000");
+    if (V > PH_MAX_V) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_sample: built for V <= %lld", (long long)PH_MAX_V);
     a = HeadArgs();
     a.dist = dist;
     a.V = V;
@@ -1489,12 +1501,8 @@ extern "C" int case_pointer_head_sample(const float* logits, const float* mix_lo
   s.first = first;
   s.last = last;
   static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&pointer_head_sample_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) !=
-        hipSuccess)
-      return case_set_error(CASE_E_LAUNCH, "case_pointer_head_sample: cannot reserve LDS");
-    attr = true;
-  }
+  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel), attr, "case_pointer_head_sample");
+  if (rc != CASE_OK) return rc;
   hipLaunchKernelGGL(pointer_head_sample_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s);
   return case_check_launch("case_pointer_head_sample");
 }
@@ -1502,32 +1510,17 @@ extern "C" int case_pointer_head_sample(const float* logits, const float* mix_lo
 extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
                                        const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
                                        float* prob, float* copy, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
-  CASE_REQUIRE(logits && mix_logits && keys && copies && lens && targets && prob && R > 0 && V > 0 && S > 0 && nmem >= 1 && R < (1ll << 31),
-               "case_pointer_head_score: bad argument");
+  CASE_REQUIRE(targets && prob, "case_pointer_head_score: bad argument");
   CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "case_pointer_head_score: %lld rows are no multiple of rows_per_source %lld",
                (long long)R, (long long)rows_per_source);
-  if (nmem > PH_MAX_MEM || V > 131071 || S > 32768)
-    return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_score: built for <= %d memories, V <= 131071, S <= 32768", PH_MAX_MEM);
   ScoreArgs a;
-  a.logits = logits;
-  a.mix_logits = mix_logits;
-  a.keys = keys;
-  int64_t total = 0;
-  for (int m = 0; m < PH_MAX_MEM; ++m) {
-    a.copy[m] = m < nmem ? copies[m] : nullptr;
-    a.len[m] = m < nmem ? lens[m] : 0;
-    total += a.len[m];
-    CASE_REQUIRE(m >= nmem || (copies[m] && lens[m] > 0), "case_pointer_head_score: null copy weights");
-  }
-  CASE_REQUIRE(total == S, "case_pointer_head_score: the memories hold %lld positions, the source map %lld", (long long)total, (long long)S);
+  const int rc = pointer_head_fill(a, "case_pointer_head_score", logits, mix_logits, keys, copies, lens, nmem, R, V, S, PS_MAX_V, "");
+  if (rc != CASE_OK) return rc;
   a.targets = targets;
   a.prob = prob;
   a.ptr = copy;
-  a.V = V;
-  a.S = S;
   a.rows_per_source = rows_per_source;
   a.pad = pad;
-  a.nmem = nmem;
   hipLaunchKernelGGL(pointer_head_score_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
   return case_check_launch("case_pointer_head_score");
 }

@@ -1933,21 +1933,28 @@ def linear_skinny(xs, w, b=None):
     return y
 
 
-def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True):
-    """logits f32 [B, V]; mix_logits f32 [B, 1 + nmem]; source_map a SortedSource over the concatenated memories; copies: list of f32
-    [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference)."""
-    B, V = logits.shape
+def _head_operands(logits, mix_logits, source_map, copies):
+    """What every pointer-head launch takes: contiguous f32 logits and mixing logits, the f32 copy weights (kept alive by the caller until the
+    call), their device pointers and lengths as C arrays, the number of memories and the source length S."""
     logits = logits if logits.is_contiguous() else logits.contiguous()
     mix_logits = mix_logits.float().contiguous()
     cs = [c.float().contiguous() for c in copies]
     n = len(cs)
     ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
-    lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
+    lens = (C.c_int64 * n)(*[c.shape[-1] for c in cs])
+    return logits, mix_logits, cs, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, source_map.keys.shape[1]
+
+
+def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True):
+    """logits f32 [B, V]; mix_logits f32 [B, 1 + nmem]; source_map a SortedSource over the concatenated memories; copies: list of f32
+    [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference)."""
+    B, V = logits.shape
+    logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_dist else None
     ids = torch.empty(B, dtype=torch.int64, device=logits.device)
-    A.call("case_pointer_head_decode", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
-           _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, source_map.keys.shape[1], _stream())
+    A.call("case_pointer_head_decode", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S,
+           _stream())
     return gen, dist, ids
 
 
@@ -1959,18 +1966,13 @@ def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=Fa
     """K24, ``pointer_head_decode`` with a top-``width`` tail: -> (gen [R, V] | None, dist [R, V] | None, cand_p f32 [R, W], cand_id int64 [R, W]),
     the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference)."""
     R, V = logits.shape
-    logits = logits if logits.is_contiguous() else logits.contiguous()
-    mix_logits = mix_logits.float().contiguous()
-    cs = [c.float().contiguous() for c in copies]
-    n = len(cs)
-    ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
-    lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
+    logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_dist else None
     cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
     cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
-    A.call("case_pointer_head_beam", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
-           _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, source_map.keys.shape[1], width, _stream())
+    A.call("case_pointer_head_beam", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p),
+           _ptr(cand_id), R, V, S, width, _stream())
     return gen, dist, cand_p, cand_id
 
 
@@ -2016,13 +2018,8 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     if logits is None:
         A.call("case_pointer_head_sample", None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw)
     else:
-        mix_logits = mix_logits.float().contiguous()
-        cs = [c.float().contiguous() for c in copies]
-        n = len(cs)
-        ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
-        lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
-        A.call("case_pointer_head_sample", _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n,
-               None, *tail, source_map.keys.shape[1], *draw)
+        src, mix_logits, cs, ptrs, lens, n, S = _head_operands(src, mix_logits, source_map, copies)
+        A.call("case_pointer_head_sample", _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, None, *tail, S, *draw)
     return gen, dist, ids, prob
 
 
@@ -2051,21 +2048,16 @@ def pointer_head_score(logits, mix_logits, source_map, rows_per_source, copies, 
         raise ValueError("pointer_head_score: %d rows, %d key rows, rows_per_source %d" % (R, keys.shape[0], rows_per_source))
     if targets.dtype != torch.int64 or targets.numel() != R:
         raise TypeError("pointer_head_score: targets must be int64 [R]")
-    logits = logits if logits.is_contiguous() else logits.contiguous()
-    mix_logits = mix_logits.float().contiguous()
     if tuple(mix_logits.shape) != (R, len(copies) + 1):
         raise ValueError("pointer_head_score: mix_logits must be [R, 1 + nmem]")
-    cs = [c.float().contiguous() for c in copies]
-    if any(c.dim() != 2 or c.shape[0] != R for c in cs):
+    if any(c.dim() != 2 or c.shape[0] != R for c in copies):
         raise ValueError("pointer_head_score: every copies[k] must be [R, len_k]")
+    logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     targets = targets.reshape(R).contiguous()
-    n = len(cs)
-    ptrs = (C.c_void_p * n)(*[c.data_ptr() for c in cs])
-    lens = (C.c_int64 * n)(*[c.shape[1] for c in cs])
     prob = torch.empty(R, dtype=torch.float32, device=logits.device)
     copy = torch.empty(R, dtype=torch.float32, device=logits.device)
-    A.call("case_pointer_head_score", _ptr(logits), _ptr(mix_logits), _ptr(keys), rows_per_source, C.cast(ptrs, C.c_void_p),
-           C.cast(lens, C.c_void_p), n, _ptr(targets), int(pad), _ptr(prob), _ptr(copy), R, V, keys.shape[1], _stream())
+    A.call("case_pointer_head_score", _ptr(logits), _ptr(mix_logits), _ptr(keys), rows_per_source, ptrs, lens, n, _ptr(targets), int(pad), _ptr(prob),
+           _ptr(copy), R, V, S, _stream())
     return prob, copy
 
 

@@ -4,6 +4,7 @@ import os
 import numpy as np
 import torch
 
+FP32_BAR = 1e-3  # the project's fp32 bar (relative)
 GOLDEN_DIR = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
@@ -85,3 +86,57 @@ def record_error(case, mode, key, rel, tol, l2=None):
     if l2 is not None:
         rec["l2_err"] = float("%.3e" % l2)
     ERRORS.setdefault(case, {}).setdefault(mode, {})[key] = rec
+
+
+# ---------------------------------------------------------------------------------------------
+# shared by the decoding tests (beam, sample, score)
+# ---------------------------------------------------------------------------------------------
+class Calls:
+    """Counts the C-ABI calls made inside the block."""
+
+    def __enter__(self):
+        from case_rg_amd import _abi
+        self.calls, self._call = {}, _abi.call
+
+        def counting(name, *a):
+            self.calls[name] = self.calls.get(name, 0) + 1
+            return self._call(name, *a)
+
+        _abi.call = counting
+        return self
+
+    def __exit__(self, *exc):
+        from case_rg_amd import _abi
+        _abi.call = self._call
+
+    def count(self, name):
+        return self.calls.get(name, 0)
+
+    @property
+    def sampled(self):
+        return self.count("case_pointer_head_sample")
+
+    @property
+    def scored(self):
+        return self.count("case_pointer_head_score")
+
+
+def special_ids(m):
+    """(BOS, EOS, UNK, PAD) of a task model's vocabulary."""
+    from case_rg_amd.common.Constants import BOS_WORD, EOS_WORD, PAD_WORD, UNK_WORD
+    return tuple(m.vocab2id[w] for w in (BOS_WORD, EOS_WORD, UNK_WORD, PAD_WORD))
+
+
+def head_inputs(R, V, lens, seed, src_low=0, design=None):
+    """Random operands of the pointer heads on the device: (logits [R, V], mix [R, 1 + nmem], SortedSource, copies, source ids on the CPU).
+    Source ids are drawn from [src_low, V); ``design(logits, src, mix)`` edits the CPU tensors in place before they are moved."""
+    from case_rg_amd import ops
+    g = torch.Generator().manual_seed(seed)
+    logits = torch.randn(R, V, generator=g) * 2.0
+    src = torch.randint(src_low, V, (R, sum(lens)), generator=g)
+    mix = torch.randn(R, 1 + len(lens), generator=g)
+    copies = [torch.softmax(torch.randn(R, n, generator=g) * 2.0, dim=-1) for n in lens]
+    if design is not None:
+        design(logits, src, mix)
+    dev = torch.device("cuda")
+    return logits.to(dev), mix.to(dev), ops.SortedSource(src.to(dev), V), [c.to(dev) for c in copies], src

@@ -10,7 +10,7 @@ import torch
 
 import beam_cases
 import cases
-from helpers import load_golden, record_error, scaled_error, to_np
+from helpers import Calls, head_inputs, load_golden, record_error, scaled_error, to_np
 from test_beam_cpu import INF, advance, backtrack, beam_search, cut_at_eos, pack, pool_insert, rel_gap
 
 pytestmark = pytest.mark.gpu
@@ -22,25 +22,6 @@ def ns():
     case_rg_amd.set_compute_dtype(torch.float32)
     case_rg_amd.set_dropout(False)
     return case_rg_amd.namespace()
-
-
-class _Calls:
-    """Counts the C-ABI calls made inside the block."""
-
-    def __enter__(self):
-        from case_rg_amd import _abi
-        self.calls, self._call = {}, _abi.call
-
-        def counting(name, *a):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return self._call(name, *a)
-
-        _abi.call = counting
-        return self
-
-    def __exit__(self, *exc):
-        from case_rg_amd import _abi
-        _abi.call = self._call
 
 
 # ---------------------------------------------------------------------------------------------
@@ -55,7 +36,7 @@ def test_fp32_beam_matches_the_reference_beam(ns, name, width):
         assert np.array_equal(to_np(b[k]), golden["in_" + k]), k
     m.eval()
     m.beam_width = width
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         out = m(dict(b), method="beam")
         again = m.do_beam(dict(b), width=width)
     assert c.calls.get("case_pointer_head_beam", 0) >= 2 and c.calls.get("case_beam_advance", 0) >= 2, "the beam kernels did not run: %s" % c.calls
@@ -109,7 +90,7 @@ def test_width_one_equals_greedy(ns, name, dtype):
         m, b = beam_cases.build(ns, torch.device("cuda"), name)
         m.eval()
         eos = m.vocab2id[EOS_WORD]
-        with torch.no_grad(), _Calls() as c:
+        with torch.no_grad(), Calls() as c:
             greedy = to_np(m(dict(b), method="test")["answer"])
             out = m.do_beam(dict(b), width=1)
         assert c.calls.get("case_pointer_head_decode", 0) >= beam_cases.T and c.calls.get("case_pointer_head_beam", 0) >= 1, "not the fused heads"
@@ -128,22 +109,18 @@ def test_width_one_equals_greedy(ns, name, dtype):
 def _head_inputs(R, V, lens, seed):
     """Logits with designed rows: row 0 plain; row 1 has exact ties among its largest logits (tokens the sources do not hold); row 2's
     pointer mass lands on its most probable tokens; row 3 is dominated by copied tokens the generator gives almost nothing."""
-    from case_rg_amd import ops
-    g = torch.Generator().manual_seed(seed)
-    S = sum(lens)
-    logits = torch.randn(R, V, generator=g) * 2.0
-    src = torch.randint(1000, V, (R, S), generator=g)
-    order = logits.argsort(dim=1, descending=True)
-    free = [int(t) for t in order[1].tolist() if t < 1000][:6]  # ids below 1000 are never in ``src``
-    logits[1, free] = logits[1].max() + 6.0  # six equal largest logits, far enough above the rest to outweigh any pointer mass ...
-    src[2, :40] = order[2, :5].repeat(8)      # the five most probable tokens, eight source positions each
-    src[3, :S // 2] = order[3, -3:].repeat(S // 2 // 3 + 1)[:S // 2]
-    mix = torch.randn(R, 1 + len(lens), generator=g)
-    mix[3, 0] = -4.0
-    mix[1, 0] = 4.0  # ... with the generator's share of row 1 near one
-    copies = [torch.softmax(torch.randn(R, n, generator=g) * 2.0, dim=-1) for n in lens]
-    dev = torch.device("cuda")
-    return logits.to(dev), mix.to(dev), ops.SortedSource(src.to(dev), V), [c.to(dev) for c in copies], src, sorted(free)
+    S, free = sum(lens), []
+
+    def design(logits, src, mix):
+        order = logits.argsort(dim=1, descending=True)
+        free.extend([int(t) for t in order[1].tolist() if t < 1000][:6])  # ids below 1000 are never in ``src``
+        logits[1, free] = logits[1].max() + 6.0  # six equal largest logits, far enough above the rest to outweigh any pointer mass ...
+        src[2, :40] = order[2, :5].repeat(8)      # the five most probable tokens, eight source positions each
+        src[3, :S // 2] = order[3, -3:].repeat(S // 2 // 3 + 1)[:S // 2]
+        mix[3, 0] = -4.0
+        mix[1, 0] = 4.0  # ... with the generator's share of row 1 near one
+
+    return head_inputs(R, V, lens, seed, src_low=1000, design=design) + (sorted(free),)
 
 
 def _head_f64(logits, mix, src, copies):
@@ -329,7 +306,7 @@ def test_production_geometry_bf16_fused_against_fallback_and_teacher_forcing():
         m, b = _prod(ns, torch.device("cuda"), kind, T=T)
         bos, eos = m.vocab2id[BOS_WORD], m.vocab2id[EOS_WORD]
         with torch.no_grad():
-            with _Calls() as c:
+            with Calls() as c:
                 fused = m.do_beam(dict(b), width=W)
             assert c.calls.get("case_pointer_head_beam", 0) >= 1 and c.calls.get("case_beam_gather", 0) >= 1
             ops.POINTER_HEAD = "off"
@@ -343,7 +320,7 @@ def test_production_geometry_bf16_fused_against_fallback_and_teacher_forcing():
 
             dec._head = recording
             try:
-                with _Calls() as c:
+                with Calls() as c:
                     fallback = m.do_beam(dict(b), width=W)
             finally:
                 del dec._head

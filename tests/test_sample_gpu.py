@@ -12,7 +12,7 @@ import torch
 
 import cases
 import sample_cases
-from helpers import load_golden, record_error, scaled_error, to_np
+from helpers import Calls, head_inputs, load_golden, record_error, scaled_error, special_ids, to_np
 from sample_cases import draw, rng_uniform24
 
 pytestmark = pytest.mark.gpu
@@ -28,34 +28,6 @@ def ns():
     return case_rg_amd.namespace()
 
 
-class _Calls:
-    """Counts the C-ABI calls made inside the block."""
-
-    def __enter__(self):
-        from case_rg_amd import _abi
-        self.calls, self._call = {}, _abi.call
-
-        def counting(name, *a):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return self._call(name, *a)
-
-        _abi.call = counting
-        return self
-
-    def __exit__(self, *exc):
-        from case_rg_amd import _abi
-        _abi.call = self._call
-
-    @property
-    def sampled(self):
-        return self.calls.get("case_pointer_head_sample", 0)
-
-
-def _special(m):
-    from case_rg_amd.common.Constants import BOS_WORD, EOS_WORD, PAD_WORD, UNK_WORD
-    return tuple(m.vocab2id[w] for w in (BOS_WORD, EOS_WORD, UNK_WORD, PAD_WORD))
-
-
 # ---------------------------------------------------------------------------------------------
 # 1. the product against the reference's sample loop
 # ---------------------------------------------------------------------------------------------
@@ -68,7 +40,7 @@ def test_fp32_sample_matches_the_reference_sample(ns, name):
         assert np.array_equal(to_np(b[key]), golden["in_" + key]), key
     m.eval()
     m.sampling = dict(num_samples=1, temperature=tau, top_k=k, top_p=pp, seed=seed)
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         out = m(dict(b), method="sample")
         again = m.do_sample(dict(b), temperature=tau, top_k=k, top_p=pp, seed=seed)
     assert c.sampled == 2 * sample_cases.T, "the sampling kernel did not run once per step: %s" % c.calls
@@ -112,7 +84,7 @@ def test_unfused_head_feeds_the_same_draw(ns, name):
 
     ops.pointer_head_sample = recording
     try:
-        with torch.no_grad(), _Calls() as c:
+        with torch.no_grad(), Calls() as c:
             fused = m.do_sample(dict(b), temperature=tau, top_k=k, top_p=pp, seed=seed)
             ops.POINTER_HEAD = "off"
             plain = m.do_sample(dict(b), temperature=tau, top_k=k, top_p=pp, seed=seed)
@@ -134,17 +106,13 @@ def test_unfused_head_feeds_the_same_draw(ns, name):
 # 2. / 5. K28 against the float64 restatement: the interval property, in both modes
 # ---------------------------------------------------------------------------------------------
 def _head_inputs(R, V, lens, seed):
-    from case_rg_amd import ops
-    g = torch.Generator().manual_seed(seed)
     S = sum(lens)
-    logits = torch.randn(R, V, generator=g) * 2.0
-    src = torch.randint(0, V, (R, S), generator=g)
-    src[0, :S // 2] = src[0, 0]          # one long run of a single token: it crosses the 1024-key chunk of the row build
-    src[1, :40] = logits[1].argsort(descending=True)[:5].repeat(8)  # pointer mass on the most probable tokens
-    mix = torch.randn(R, 1 + len(lens), generator=g)
-    copies = [torch.softmax(torch.randn(R, n, generator=g) * 2.0, dim=-1) for n in lens]
-    dev = torch.device("cuda")
-    return logits.to(dev), mix.to(dev), ops.SortedSource(src.to(dev), V), [c.to(dev) for c in copies]
+
+    def design(logits, src, mix):
+        src[0, :S // 2] = src[0, 0]          # one long run of a single token: it crosses the 1024-key chunk of the row build
+        src[1, :40] = logits[1].argsort(descending=True)[:5].repeat(8)  # pointer mass on the most probable tokens
+
+    return head_inputs(R, V, lens, seed, design=design)[:4]
 
 
 def _interval(p, params, u, j, tol):
@@ -185,7 +153,7 @@ def test_kernel_draws_inside_the_restated_interval(V, R):
             u = torch.tensor(us, dtype=torch.float32, device="cuda")
             assert np.array_equal(to_np(u).astype(np.float64), us)
             ended = torch.zeros(R, dtype=torch.uint8, device="cuda")
-            with _Calls() as c:
+            with Calls() as c:
                 gen, dist, ids, prob = ops.pointer_head_sample(logits, mix, sm, copies, ended, False, False, -1, -1, 0, *params, uniforms=u,
                                                                want_gen=True, want_dist=True)
                 _, dist2, ids2, prob2 = ops.pointer_head_sample(None, None, None, None, ended, False, False, -1, -1, 0, *params, uniforms=u,
@@ -222,7 +190,7 @@ def test_loop_conventions_and_the_counter_uniform_in_the_kernel():
 
     def step(ended, first, last):
         e = torch.tensor(ended, dtype=torch.uint8, device=dev)
-        with _Calls() as c:
+        with Calls() as c:
             _, _, ids, prob = ops.pointer_head_sample(None, None, None, None, e, first, last, EOS, UNK, PAD, 1.0, 0, 1.0, uniforms=u, dist_in=d)
         assert c.sampled == 1
         return ids.tolist(), e.tolist(), prob.tolist()
@@ -248,7 +216,7 @@ def test_ties_and_zero_entries():
     R, V = 4096, 1031
     ended = torch.zeros(R, dtype=torch.uint8, device=dev)
     flat = torch.full((R, V), 1.0 / V, device=dev)
-    with _Calls() as c:
+    with Calls() as c:
         _, _, ids, prob = ops.pointer_head_sample(None, None, None, None, ended, False, False, -1, -1, 0, 1.0, 5, 1.0, rng=(5, 0, None), dist_in=flat)
     assert c.sampled == 1
     assert sorted(set(ids.tolist())) == [0, 1, 2, 3, 4], "a uniform row with top_k = 5 keeps its five lowest ids: %s" % sorted(set(ids.tolist()))
@@ -258,7 +226,7 @@ def test_ties_and_zero_entries():
     sparse = torch.zeros(R, V, device=dev)
     for i, x in zip(where, p):
         sparse[:, i] = x
-    with _Calls() as c:
+    with Calls() as c:
         runs = [ops.pointer_head_sample(None, None, None, None, ended, False, False, -1, -1, 0, 1.0, 0, 1.0, rng=(17, 0, None), dist_in=sparse)[2]
                 for _ in range(2)]
         filtered = ops.pointer_head_sample(None, None, None, None, ended, False, False, -1, -1, 0, 0.7, 0, 0.99, rng=(17, 0, None), dist_in=sparse)[2]
@@ -288,9 +256,9 @@ def test_one_kept_entry_equals_greedy(ns, name, dtype):
     try:
         m, b = sample_cases.build(ns, torch.device("cuda"), name)
         m.eval()
-        _, eos, unk, _ = _special(m)
+        _, eos, unk, _ = special_ids(m)
         T = sample_cases.T
-        with torch.no_grad(), _Calls() as c:
+        with torch.no_grad(), Calls() as c:
             greedy = to_np(m(dict(b), method="test")["answer"])
             outs = [m.do_sample(dict(b), top_k=1, seed=3), m.do_sample(dict(b), top_p=1e-6, seed=4)]
         assert c.calls.get("case_pointer_head_decode", 0) >= T and c.sampled == 2 * T, "not the fused heads: %s" % c.calls
@@ -350,10 +318,10 @@ def test_several_samples_per_item(ns, name):
     kind, N, seed = sample_cases.SAMPLE_CASES[name][0], 4, 29
     m, b = sample_cases.build(ns, torch.device("cuda"), name)
     m.eval()
-    _, eos, unk, pad = _special(m)
+    _, eos, unk, pad = special_ids(m)
     B, T = sample_cases.ITEMS, sample_cases.T
     R = B * N
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         out = m.do_sample(dict(b), num_samples=N, seed=seed)
     assert c.sampled == T
     assert out["samples"].shape == (B, N, T) and out["sample_probs"].shape == (B, N, T) and out["sample_scores"].shape == (B, N)
@@ -369,7 +337,7 @@ def test_several_samples_per_item(ns, name):
     np.testing.assert_allclose(to_np(out["sample_scores"]), want_scores, rtol=1e-5, atol=1e-6)
     u = rng_uniform24(seed, np.arange(T * R, dtype=np.uint64)).reshape(T, R)  # counter t R + b N + n
     # at the same number of rows nothing rounds differently: handing every row the uniform of its counter repeats the pass bit for bit
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         same = m.do_sample(dict(b), num_samples=N, uniforms=torch.tensor(u, dtype=torch.float32, device="cuda"))
     assert c.sampled == T
     for key in ("samples", "sample_probs", "sample_scores"):
@@ -389,7 +357,7 @@ def test_several_samples_per_item(ns, name):
     assert (steps == T).sum() * 2 >= R, "fewer than half the rows are decisive throughout: %s" % steps
     for n in range(N):
         un = torch.tensor(u.reshape(T, B, N)[:, :, n], dtype=torch.float32, device="cuda")
-        with torch.no_grad(), _Calls() as c:
+        with torch.no_grad(), Calls() as c:
             single = m.do_sample(dict(b), uniforms=un)
         assert c.sampled == T
         one = to_np(single["samples"][:, 0])
@@ -417,7 +385,7 @@ def test_pass_stops_once_every_row_has_ended(ns):
         outs = []
         for every in (1, 1 << 30):
             dec.eos_check_every = every
-            with torch.no_grad(), _Calls() as c:
+            with torch.no_grad(), Calls() as c:
                 outs.append(m.do_sample(dict(one), temperature=tau, top_k=k, top_p=pp, uniforms=u))
             assert c.sampled == dec.last_sample_steps == (1 if every == 1 else T), (every, c.calls, dec.last_sample_steps)
     finally:
@@ -439,10 +407,10 @@ def test_production_rows_draw_inside_the_oracle_interval(ns):
     m = cases._prod_test_model(ns, dev, 311, kind, cases.PROD_TEST_GAIN[kind]).eval()
     m.max_target_length = T
     b = cases._prod_test_batch(dev, 312, kind)
-    _, eos, unk, pad = _special(m)
+    _, eos, unk, pad = special_ids(m)
     B = b["query"].shape[0]
     R = B * N
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         out = m.do_sample(dict(b), num_samples=N, seed=seed)
     assert c.sampled == T and B == 2
     samples = to_np(out["samples"])
@@ -509,7 +477,7 @@ def test_sampled_pass_replays_from_a_captured_graph(ns):
         torch.cuda.current_stream().wait_stream(side)
         graph, static = torch.cuda.CUDAGraph(), {}
         config.manual_seed(77)
-        with torch.cuda.graph(graph), _Calls() as c:
+        with torch.cuda.graph(graph), Calls() as c:
             static.update(model.do_sample(dict(b), num_samples=N, top_k=20, temperature=0.9))
         assert c.sampled == T == dec.last_sample_steps, "a captured pass runs the fixed T steps"
         return graph, static

@@ -16,12 +16,11 @@ import torch
 import cases
 import sample_cases
 import score_cases
-from helpers import load_golden, record_error, scaled_error, to_np
+from helpers import FP32_BAR, Calls, load_golden, record_error, scaled_error, special_ids, to_np
 
 pytestmark = pytest.mark.gpu
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FP32_BAR = 1e-3  # the project's fp32 bar
 
 
 def _measured(key, value, bar=None):
@@ -51,29 +50,6 @@ def ns():
     case_rg_amd.set_compute_dtype(torch.float32)
     case_rg_amd.set_dropout(False)
     return case_rg_amd.namespace()
-
-
-class _Calls:
-    """Counts the C-ABI calls made inside the block."""
-
-    def __enter__(self):
-        from case_rg_amd import _abi
-        self.calls, self._call = {}, _abi.call
-
-        def counting(name, *a):
-            self.calls[name] = self.calls.get(name, 0) + 1
-            return self._call(name, *a)
-
-        _abi.call = counting
-        return self
-
-    def __exit__(self, *exc):
-        from case_rg_amd import _abi
-        _abi.call = self._call
-
-    @property
-    def scored(self):
-        return self.calls.get("case_pointer_head_score", 0)
 
 
 class _Unfused:
@@ -110,7 +86,7 @@ def fixture_models(ns):
 @pytest.mark.parametrize("name", list(score_cases.SCORE_CASES))
 def test_fp32_scores_match_the_reference(fixture_models, name, head):
     golden, m, b, cands = fixture_models[name]
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         if head == "unfused":
             with _Unfused():
                 out = m.do_score(dict(b), cands)
@@ -263,7 +239,7 @@ def test_kernel_matches_the_float64_restatement(V, R, rps):
                 ids = [special[(first + i) % len(special)] for i in range(R)]
                 targets = torch.tensor(ids, dtype=torch.int64, device="cuda")
                 for pad in (0, -1):
-                    with _Calls() as c:
+                    with Calls() as c:
                         prob, ptr = ops.pointer_head_score(logits, mix, sm, rps, copies, targets, pad=pad)
                         prob2, ptr2 = ops.pointer_head_score(logits, mix, sm, rps, copies, targets, pad=pad)
                     assert c.scored == 2
@@ -309,11 +285,6 @@ def test_kernel_matches_the_greedy_heads_row(V):
 # ---------------------------------------------------------------------------------------------
 # 5. the cached decoding step against the full-prefix pass
 # ---------------------------------------------------------------------------------------------
-def _special(m):
-    from case_rg_amd.common.Constants import BOS_WORD, EOS_WORD, PAD_WORD, UNK_WORD
-    return tuple(m.vocab2id[w] for w in (BOS_WORD, EOS_WORD, UNK_WORD, PAD_WORD))
-
-
 def _drawn_positions(samples, unk, pad):
     """Where ``sample_probs`` is the probability of the EMITTED token: K28 records the probability of the token it DREW, and the loop emits
     something else at t = 0 (UNK for a drawn EOS), at the last step (EOS is forced) and behind the end (PAD)."""
@@ -343,7 +314,7 @@ def test_rescoring_reproduces_the_cached_steps_probabilities(ns, name):
     the costs of the beam search's finished hypotheses are the rescored ones."""
     m, b = sample_cases.build(ns, torch.device("cuda"), name)
     m.eval()
-    _, eos, unk, pad = _special(m)
+    _, eos, unk, pad = special_ids(m)
     with torch.no_grad():
         drawn = m.do_sample(dict(b), num_samples=3, seed=5)
         again = m.do_score(dict(b), drawn["samples"])
@@ -379,7 +350,7 @@ def test_rescoring_production_rows_in_bf16():
     with _Mode("bf16_auto"):
         m = cases._prod_test_model(case_rg_amd.namespace(), dev, 311, kind, cases.PROD_TEST_GAIN[kind]).eval()
         b = cases._prod_test_batch(dev, 312, kind)
-        _, eos, unk, pad = _special(m)
+        _, eos, unk, pad = special_ids(m)
         with torch.no_grad():
             drawn = m.do_sample(dict(b), num_samples=3, seed=9)
             again = m.do_score(dict(b), drawn["samples"])
@@ -409,7 +380,7 @@ def test_chunked_head_agrees_with_the_default(fixture_models, name):
     _, m, b, cands = fixture_models[name]
     dec = m.response_generation.decoder
     assert dec.score_chunk_rows == 2048
-    with torch.no_grad(), _Calls() as c:
+    with torch.no_grad(), Calls() as c:
         whole = m.do_score(dict(b), cands)
         n_whole = c.scored
         dec.score_chunk_rows = 5
@@ -456,7 +427,7 @@ def test_differentiable_pass_reaches_the_parameters(ns, name):
     with torch.no_grad():
         fused = m.do_score(dict(b), cands)
     m.zero_grad()
-    with _Calls() as c:
+    with Calls() as c:
         out = m.do_score(dict(b), cands)
     assert c.scored == 0 and out["loss"].requires_grad
     out["loss"].sum().backward()
@@ -487,7 +458,7 @@ def test_scoring_pass_replays_from_a_captured_graph(fixture_models):
             m.do_score(dict(b), cands)  # warm-up on the capture stream
         torch.cuda.current_stream().wait_stream(side)
         graph, static = torch.cuda.CUDAGraph(), {}
-        with torch.cuda.graph(graph), _Calls() as c:
+        with torch.cuda.graph(graph), Calls() as c:
             static.update(m.do_score(dict(b), cands))
         assert c.scored == 1
         for _ in range(2):
