@@ -14,6 +14,7 @@ from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, sampling_params
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
+from ..evaluation.rouge_ids import consensus_answers
 
 
 class CaSETransformerSeqDecoder(PointerDecoderCore):
@@ -168,6 +169,7 @@ class CaSE(nn.Module):
         self.vocab2id = vocab2id
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
+        self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -232,6 +234,17 @@ class CaSE(nn.Module):
         rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling)
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, **sampling):
+        """Consensus (minimum-Bayes-risk) selection under ROUGE-L (eval mode only): the answer is the candidate of a pool with the highest
+        expected ROUGE-L F against the pool, instead of the pool's slot 0.  ``pool="sample"``: ``do_sample`` with ``self.sampling`` overridden
+        by ``**sampling`` (``num_samples`` defaults to ``self.consensus_samples``); ``pool="beam"``: ``do_beam`` (``width=`` may be given), the
+        pool is ``beam_answers`` and the empty slots (``beam_scores`` = +inf) are invalid; explicit ``candidates`` int64 [B, N, T]: no decoding,
+        only the encode stages run for ``rank``.  ``valid`` bool [B, N] and ``weights`` f32 [B, N] (default uniform; e.g. the posterior
+        exp(-length x ``sample_scores``)) as in ``evaluation.consensus``.  N <= 64, T <= 256, ids < 2^31; an empty candidate counts as [UNK].
+        -> the pool's dict with ``answer`` [B, T] replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility`` [B, N] (-inf where
+        invalid) and ``pairwise_f`` [B, N, N].  Nothing is read back: with a sample pool at an integer ``seed`` the pass captures into one graph."""
+        return consensus_answers(self, data, lambda d: self._encode_select_extract(d)[2][0], pool, candidates, valid, weights, **sampling)
+
     def do_score(self, data, answers=None):
         """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at
         the positions that are not scored -- the layout of ``data['response']`` (the default), of ``do_beam``'s ``beam_answers`` and of
@@ -261,3 +274,5 @@ class CaSE(nn.Module):
             return self.do_sample(data, **self.sampling)
         elif method == 'score':
             return self.do_score(data)
+        elif method == 'consensus':
+            return self.do_consensus(data)

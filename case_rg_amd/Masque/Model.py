@@ -9,6 +9,7 @@ from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, sampling_params
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair
+from ..evaluation.rouge_ids import consensus_answers
 
 
 class MasqueTransformerSeqDecoder(PointerDecoderCore):
@@ -116,6 +117,7 @@ class Masque(nn.Module):
         self.vocab2id = vocab2id
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
+        self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -175,6 +177,12 @@ class Masque(nn.Module):
         rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling)
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, **sampling):
+        """Consensus (minimum-Bayes-risk) selection under ROUGE-L over a sample pool, a beam pool or explicit ``candidates`` (eval mode only;
+        see CaSE.do_consensus): the pool's dict with ``answer`` replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility``
+        [B, N] and ``pairwise_f`` [B, N, N]."""
+        return consensus_answers(self, data, lambda d: self._encode_select(d)[2][0], pool, candidates, valid, weights, **sampling)
+
     def do_score(self, data, answers=None):
         """The probability of given answers under the model (eval mode only; see CaSE.do_score): ``answers`` int64 [B, T'] or [B, N, T'],
         PAD (0) = not scored, default ``data['response']`` -> ``rank``, ``token_probs`` / ``copy_probs`` [B, N, T'], ``scores`` [B, N],
@@ -198,3 +206,5 @@ class Masque(nn.Module):
             return self.do_sample(data, **self.sampling)
         elif method == 'score':
             return self.do_score(data)
+        elif method == 'consensus':
+            return self.do_consensus(data)

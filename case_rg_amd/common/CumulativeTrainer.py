@@ -269,3 +269,29 @@ class CumulativeTrainer(object):
             return dict(nll=float('nan'), perplexity=float('nan'), tokens=0)
         nll = float(total) / int(tokens)  # (the one read-back of the evaluation)
         return dict(nll=nll, perplexity=math.exp(nll), tokens=int(tokens))
+
+    def evaluate_rouge(self, dataset, collate_fn, batch_size, method='test', references='response'):
+        """ROUGE-L of ``model(data, method)['answer']`` against ``data[references]`` (int64 [B, T'] or [B, M, T'], all-PAD rows = no ground truth
+        there) without building a Python string: ``evaluation.eval_rouge_l_ids`` per batch, the sum kept on the device, one read-back at the
+        end -> dict(rouge_l = the mean of the per-item best F x 100 rounded to 2 decimals -- ``evaluation.eval_rouge_l``'s number for
+        ``predict`` + ``to_sentence`` --, items = the items counted).  One process, under no_grad in eval mode; the model's mode is restored
+        afterwards."""
+        from ..evaluation.rouge_ids import eval_rouge_l_ids, model_specials
+        was_training = self.model.training
+        self.model.eval()
+        specials = model_specials(self.model.vocab2id)
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    out = self.model(data, method=method)
+                    part = eval_rouge_l_ids(out['answer'], data[references], specials).sum()
+                    total = part if total is None else total + part
+                    items += out['answer'].shape[0]
+        finally:
+            self.model.train(was_training)
+        if items == 0:
+            return dict(rouge_l=float('nan'), items=0)
+        return dict(rouge_l=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)

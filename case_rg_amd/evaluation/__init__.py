@@ -1,2 +1,4 @@
-"""Answer-quality metrics of the reference's evaluation scripts that the acceptance bar names (ROUGE-L)."""
+"""Answer-quality metrics of the reference's evaluation scripts that the acceptance bar names (ROUGE-L): on the host over token strings
+(``rouge``), and on the device over token ids together with the consensus pick over a pool of candidates (``rouge_ids``)."""
 from .rouge import eval_rouge_l, lcs_length, rouge_l  # noqa: F401
+from .rouge_ids import consensus, eval_rouge_l_ids, rouge_l_ids  # noqa: F401

@@ -1,0 +1,108 @@
+"""ROUGE-L on token ids, on the device, and consensus (minimum-Bayes-risk) answer selection over a pool of decoded candidates.
+
+``rouge.py`` beside this file is the host form (token strings, one numpy DP per pair, after a device-to-host copy).  Here the ids stay where
+the decoders left them: ``ops.sentence_compact`` applies ``to_sentence``'s filter (drop BOS / PAD, cut at EOS), K30 (``ops.lcs_pairs``) gives
+the LCS length and the F value of every (hypothesis, reference) pair, and K31 (``ops.consensus_pick``) picks, per item, the candidate with
+the highest expected ROUGE-L against its pool.  Nothing is read back to the host, so a decoding pass followed by any of these still captures
+into one graph.
+
+Conventions: an EMPTY HYPOTHESIS is the single token UNK (``to_sentence``'s rule); an EMPTY REFERENCE ROW is absent (a ragged number of
+ground truths is padded with all-PAD rows).  Limits: hypotheses of at most 256 positions, ids in [0, 2^31)."""
+import torch
+
+from .. import ops
+
+
+def _compact(ids, bos, pad, eos, unk=None):
+    """ids int64 [B, N, T] -> (front-packed ids [B, N, T], lengths int32 [B, N]); with ``unk`` an empty row becomes [UNK]."""
+    B, N, T = ids.shape
+    kept, count = ops.sentence_compact(ids.reshape(B * N, T), bos, pad, eos)
+    if unk is not None:
+        empty = count.eq(0)
+        kept[:, 0] = torch.where(empty, torch.full_like(kept[:, 0], unk), kept[:, 0])
+        count = count.clamp_min(1)
+    return kept.view(B, N, T), count.view(B, N)
+
+
+def _pool(ids, what):
+    if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() not in (2, 3):
+        raise TypeError("%s must be an int64 tensor [B, T] or [B, N, T]" % what)
+    return ids.unsqueeze(1) if ids.dim() == 2 else ids
+
+
+def rouge_l_ids(hyp, ref, specials):
+    """hyp int64 [B, T] or [B, N, T], ref int64 [B, T'] or [B, M, T'] (raw ids on the device, as the decoders and the batches hold them),
+    specials = (bos, pad, eos, unk) -> dict(lcs int32, f f32, p f64, r f64: all [B, N, M]; ref_valid bool [B, M]).  f / p / r are
+    ``rouge.rouge_l``'s of hypothesis n against reference m; an absent reference (``ref_valid`` False) reads 0 everywhere."""
+    bos, pad, eos, unk = specials
+    hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
+    if hyp.shape[0] != ref.shape[0]:
+        raise ValueError("rouge_l_ids: %d hypothesis items, %d reference items" % (hyp.shape[0], ref.shape[0]))
+    if hyp.shape[2] > ops.LCS_MAX_T:
+        raise ValueError("rouge_l_ids: hypotheses of up to %d positions (got %d)" % (ops.LCS_MAX_T, hyp.shape[2]))
+    a, a_len = _compact(hyp, bos, pad, eos, unk)
+    b, b_len = _compact(ref, bos, pad, eos)
+    lcs, f = ops.lcs_pairs(a, a_len, b, b_len)
+    n = lcs.double()
+    return dict(lcs=lcs, f=f, p=n / a_len.double().unsqueeze(2), r=n / b_len.clamp_min(1).double().unsqueeze(1), ref_valid=b_len.gt(0))
+
+
+def eval_rouge_l_ids(hyp, ref, specials):
+    """hyp int64 [B, T], ref int64 [B, M, T'] (or [B, T']: one ground truth) -> f64 [B] on the device: per item the best F x 100 over its
+    present references (0 for an item without one).  Its mean rounded to 2 decimals is ``rouge.eval_rouge_l``'s number (F is K30's f32
+    rounding of the host's f64 value, so a per-item term is within 1.2e-5 of the host's)."""
+    if hyp.dim() != 2:
+        raise TypeError("eval_rouge_l_ids: hyp must be int64 [B, T], one answer per item")
+    out = rouge_l_ids(hyp, ref, specials)
+    f = out["f"][:, 0].double()
+    return torch.where(out["ref_valid"], f, torch.zeros_like(f)).max(dim=1)[0] * 100
+
+
+def consensus(candidates, specials, valid=None, weights=None):
+    """candidates int64 [B, N, T] (raw ids: ``do_sample``'s ``samples``, ``do_beam``'s ``beam_answers``), specials = (bos, pad, eos, unk),
+    valid bool [B, N] (default: all), weights f32 [B, N] (default: uniform; e.g. a posterior exp(-len x sample_scores)) ->
+    dict(answer int64 [B, T] = the raw row of the pick, consensus_index int64 [B], consensus_utility f32 [B, N], pairwise_f f32 [B, N, N]).
+    The pick of item b maximises  sum_m w[b, m] F(candidate n as the hypothesis, m as the reference) / sum_m w[b, m]  over the valid
+    candidates, the self term included, the lowest index on ties; an invalid candidate reads -inf and is never picked."""
+    bos, pad, eos, unk = specials
+    if not torch.is_tensor(candidates) or candidates.dtype != torch.int64 or candidates.dim() != 3:
+        raise TypeError("consensus: candidates must be an int64 tensor [B, N, T]")
+    N, T = candidates.shape[1:]
+    if not ops.consensus_supported(N, T):
+        raise ValueError("consensus: pools of up to %d candidates of up to %d positions (got %d x %d)" % (ops.CONSENSUS_MAX_N, ops.LCS_MAX_T, N, T))
+    kept, count = _compact(candidates, bos, pad, eos, unk)
+    _, f = ops.lcs_pairs(kept, count, kept, count)
+    weights = None if weights is None else weights.to(device=candidates.device, dtype=torch.float32)
+    utility, index, answer = ops.consensus_pick(f, weights, valid, candidates)
+    return dict(answer=answer, consensus_index=index, consensus_utility=utility, pairwise_f=f)
+
+
+def model_specials(vocab2id):
+    """(bos, pad, eos, unk) of a task model's vocabulary."""
+    from ..common.Constants import BOS_WORD, EOS_WORD, PAD_WORD, UNK_WORD
+    return tuple(vocab2id[w] for w in (BOS_WORD, PAD_WORD, EOS_WORD, UNK_WORD))
+
+
+def consensus_answers(model, data, rank_of, pool="sample", candidates=None, valid=None, weights=None, **sampling):
+    """``do_consensus`` of the task models (CaSE, Masque): build the pool with the model's own decoders (or take ``candidates``), then
+    ``consensus``.  ``rank_of(data)``: the model's passage ranking from its encode stages alone."""
+    if model.training:
+        raise ValueError("do_consensus runs in eval mode: call model.eval() first")
+    if candidates is not None:
+        if sampling:
+            raise TypeError("do_consensus: explicit candidates take no decoding arguments (%s)" % ", ".join(sorted(sampling)))
+        out, pool_ids = {'rank': rank_of(data)}, candidates.to(data['query'].device)
+    elif pool == "sample":
+        params = dict(model.sampling, num_samples=model.consensus_samples)
+        params.update(sampling)
+        out = model.do_sample(data, **params)
+        pool_ids = out['samples']
+    elif pool == "beam":
+        out = model.do_beam(data, **sampling)
+        pool_ids = out['beam_answers']
+        finite = torch.isfinite(out['beam_scores'])
+        valid = finite if valid is None else finite & valid.to(finite.device).bool()
+    else:
+        raise ValueError("do_consensus: pool must be 'sample' or 'beam' (or give candidates), not %r" % (pool,))
+    out.update(consensus(pool_ids, model_specials(model.vocab2id), valid=valid, weights=weights))
+    return out

@@ -2233,3 +2233,58 @@ def sentence_compact(ids, bos, pad, eos):
     n = torch.empty(B, dtype=torch.int32, device=ids.device)
     A.call("case_sentence_compact", _ptr(ids), _ptr(out), _ptr(n), B, T, bos, pad, eos, _stream())
     return out, n
+
+
+# K30 / K31: ROUGE-L on token ids and the consensus pick over a pool of candidates
+CONSENSUS_MAX_N, LCS_MAX_T = 64, 256
+
+
+def consensus_supported(N, T):
+    """A pool of N candidates of T positions: K31 holds a pool in one wave, K30 a hypothesis in 4 x 64 match-mask bits."""
+    return 1 <= N <= CONSENSUS_MAX_N and 1 <= T <= LCS_MAX_T and bool(A.lib.case_abi_features() & A.FEAT_CONSENSUS)
+
+
+def lcs_pairs(a, a_len, b, b_len):
+    """K30: a int64 [B, N, Ta] / a_len int32 [B, N] (front-packed hypotheses and their lengths, as ``sentence_compact`` writes them), b int64
+    [B, M, Tb] / b_len int32 [B, M] (references) -> (lcs int32 [B, N, M], f f32 [B, N, M]): the LCS length and the ROUGE-L F of every pair
+    (evaluation.rouge's, in f64, rounded once).  Ta <= 256; ids must lie in [0, 2^31) (not checked: they are compared on 32 bits)."""
+    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
+        raise TypeError("lcs_pairs: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
+    B, N, Ta = a.shape
+    M, Tb = b.shape[1], b.shape[2]
+    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
+        raise TypeError("lcs_pairs: the lengths must be int32 [B, N] and [B, M]")
+    if Ta > LCS_MAX_T:
+        raise ValueError("lcs_pairs: hypotheses of up to %d positions (got %d)" % (LCS_MAX_T, Ta))
+    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
+    lcs = torch.empty(B, N, M, dtype=torch.int32, device=a.device)
+    f = torch.empty(B, N, M, dtype=torch.float32, device=a.device)
+    A.call("case_lcs_pairs", _ptr(a), _ptr(a_len), _ptr(b), _ptr(b_len), _ptr(lcs), _ptr(f), B, N, M, Ta, Tb, _stream())
+    return lcs, f
+
+
+def consensus_pick(f, weights, valid, candidates):
+    """K31: f f32 [B, N, N] (pairwise utility, candidate n as the hypothesis, m as the reference), weights f32 [B, N] or None (uniform),
+    valid bool [B, N] or None (all), candidates int64 [B, N, T] -> (utility f32 [B, N] = the weighted mean of f[b, n, :] over the valid m,
+    -inf for an invalid n; index int64 [B] = its argmax, the lowest index on ties, 0 without a valid candidate; answer int64 [B, T] =
+    candidates[b, index[b]])."""
+    if f.dtype != torch.float32 or f.dim() != 3 or f.shape[1] != f.shape[2]:
+        raise TypeError("consensus_pick: f must be f32 [B, N, N]")
+    B, N = f.shape[:2]
+    if candidates.dtype != torch.int64 or candidates.dim() != 3 or tuple(candidates.shape[:2]) != (B, N):
+        raise TypeError("consensus_pick: candidates must be int64 [B, N, T]")
+    if N > CONSENSUS_MAX_N:
+        raise ValueError("consensus_pick: pools of up to %d candidates (got %d)" % (CONSENSUS_MAX_N, N))
+    if weights is not None and (weights.dtype != torch.float32 or tuple(weights.shape) != (B, N)):
+        raise TypeError("consensus_pick: weights must be f32 [B, N]")
+    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, N)):
+        raise TypeError("consensus_pick: valid must be bool [B, N]")
+    T = candidates.shape[2]
+    f, candidates = (t if t.is_contiguous() else t.contiguous() for t in (f, candidates))
+    weights = None if weights is None else weights.contiguous()
+    utility = torch.empty(B, N, dtype=torch.float32, device=f.device)
+    index = torch.empty(B, dtype=torch.int64, device=f.device)
+    answer = torch.empty(B, T, dtype=torch.int64, device=f.device)
+    A.call("case_consensus_pick", _ptr(f), _ptr(weights), _ptr(_u8(valid)), _ptr(candidates), _ptr(utility), _ptr(index), _ptr(answer), B, N, T,
+           _stream())
+    return utility, index, answer

@@ -73,7 +73,8 @@ enum {
   CASE_FEAT_LINEAR_SKINNY = 1u << 17,     /* case_linear_skinny */
   CASE_FEAT_BEAM_DECODE = 1u << 18,       /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
   CASE_FEAT_SAMPLE_DECODE = 1u << 19,     /* K28 case_pointer_head_sample */
-  CASE_FEAT_POINTER_SCORE = 1u << 20      /* K29 case_pointer_head_score */
+  CASE_FEAT_POINTER_SCORE = 1u << 20,     /* K29 case_pointer_head_score */
+  CASE_FEAT_CONSENSUS = 1u << 21          /* K30 / K31 case_lcs_pairs / case_consensus_pick */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -657,6 +658,29 @@ int case_encoder_chain(const CaseEncoderChainDesc* d, const void* x_in, const vo
  * copy of (out, len) replaces the reference's `.item()` per generated token.  Pass -1 for a special id the vocabulary lacks. */
 int case_sentence_compact(const int64_t* ids, int64_t* out, int32_t* len, int64_t B, int64_t T, int64_t bos, int64_t pad,
                           int64_t eos, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Consensus (minimum-Bayes-risk) selection over a pool of candidates, and ROUGE-L on token ids (CASE_FEAT_CONSENSUS; purely additive,
+ * generation 600 unchanged).  The metric is evaluation/Rouge.py:65-108 (LCS) and :186-206 (F-measure) on ids instead of words.
+ * K30 case_lcs_pairs: for every item b, hypothesis n and reference m
+ *     lcs[b, n, m] = the length of the longest common subsequence of a[b, n, 0 .. a_len[b, n]) and b[b, m, 0 .. b_len[b, m]);
+ *     r = lcs / b_len, p = lcs / a_len, beta = p / (r + 1e-12), f[b, n, m] = (1 + beta^2) r p / (r + beta^2 p + 1e-12)
+ *   evaluated in f64 in this order and rounded once to f32; a_len == 0 or b_len == 0 gives lcs = 0 and f = 0.
+ *   a int64 [B, N, Ta], b int64 [B, M, Tb]: front-packed ids (what case_sentence_compact writes); a_len [B, N], b_len [B, M] int32 (clamped to
+ *   0 .. Ta / Tb); lcs int32 and f f32 [B, N, M].  Ids are compared on their low 32 bits: the caller guarantees 0 <= id < 2^31 (not checked).
+ *   One wave per hypothesis holds it as 64-bit match masks, so Ta <= 256 (CASE_E_UNSUPPORTED beyond); Tb is a loop count without such a
+ *   limit.  Integer arithmetic up to the one F evaluation: two launches give the same bits.
+ * K31 case_consensus_pick: with f [B, N, N] the pairwise utility of a pool against itself (candidate n as the hypothesis, m as the reference,
+ *   the self term included), w f32 [B, N] (NULL: uniform) and valid u8 [B, N] (NULL: all valid)
+ *     utility[b, n] = sum_{valid m} w[b, m] f[b, n, m] / sum_{valid m} w[b, m]   (f32, m ascending; 0 when the weights sum to 0);
+ *     -inf for an invalid n;  index[b] (int64) = the argmax with the lowest index among equals, 0 for an item without a valid candidate;
+ *     answer[b, 0 .. T) = cand[b, index[b], 0 .. T)   (cand int64 [B, N, T]: the raw rows, copied bit for bit).
+ *   One wave per item: N <= 64 (CASE_E_UNSUPPORTED beyond).
+ * ------------------------------------------------------------------------------------------- */
+int case_lcs_pairs(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* lcs, float* f, int64_t B,
+                   int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream);
+int case_consensus_pick(const float* f, const float* w, const uint8_t* valid, const int64_t* cand, float* utility, int64_t* index,
+                        int64_t* answer, int64_t B, int64_t N, int64_t T, case_stream_t stream);
 
 #ifdef __cplusplus
 }
