@@ -11,7 +11,7 @@ import torch.nn as nn
 from .. import config, ops
 from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
-from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, sampling_params
+from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, no_repeat_ngram_param, sampling_params
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
 from ..evaluation.rouge_ids import consensus_answers
@@ -53,9 +53,9 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
-                score_index=None):
+                score_index=None, no_repeat_ngram=0):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T))
+                         score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram)
 
 
 class RelevantPassageSelection(nn.Module):
@@ -131,7 +131,7 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
-               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
+               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -146,7 +146,8 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep[0], passage_rep[0]], self.BOS, self.UNK, source_map,
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
-                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index)
+                            encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
+                            no_repeat_ngram=no_repeat_ngram)
 
 
 class CaSE(nn.Module):
@@ -170,6 +171,9 @@ class CaSE(nn.Module):
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
+        # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
+        # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
+        self.no_repeat_ngram = 0
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -207,20 +211,27 @@ class CaSE(nn.Module):
                                              output=None, **mode)
         return rg, ps[0]
 
-    def do_test(self, data):
-        rg, rank = self._respond(data, max_target_length=self.max_target_length)
+    def _ngram(self, no_repeat_ngram):
+        """The checked n-gram ban of a decoding call: the keyword, or the model's attribute when it is None."""
+        return no_repeat_ngram_param(self.no_repeat_ngram if no_repeat_ngram is None else no_repeat_ngram, self.max_target_length)
+
+    def do_test(self, data, no_repeat_ngram=None):
+        """Greedy decoding.  ``no_repeat_ngram`` (None = ``self.no_repeat_ngram``; 0 = off): at every step the tokens that would complete an
+        n-gram the answer already holds get probability 0 before the argmax (K32); max_target_length <= 256 with it on."""
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, no_repeat_ngram=self._ngram(no_repeat_ngram))
         return {'answer': rg[3], 'rank': rank}
 
     do_infer = do_test  # BASELINE.json's wording
 
-    def do_beam(self, data, width=None):
+    def do_beam(self, data, width=None, no_repeat_ngram=None):
         """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``: ``width`` hypotheses per
         item ranked by length-normalised cost, retired on EOS): the ``do_test`` dict plus ``beam_score`` [B] (the answer's cum_cost / length),
         ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer)."""
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width)
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width,
+                                 no_repeat_ngram=self._ngram(no_repeat_ngram))
         return {'answer': rg[3], 'rank': rank, 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
 
-    def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None):
+    def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None, no_repeat_ngram=None):
         """``do_test`` with every token DRAWN from the model's distribution (the reference's common/Generations.py ``sample`` loop; the draw is
         from the mixed pointer-generator distribution itself after ``temperature`` / ``top_k`` (0 = off) / ``top_p`` (1 = off), not from the
         reference's softmax of it): the ``do_test`` dict plus ``samples`` [B, N, T], ``sample_probs`` [B, N, T] (the model's unfiltered
@@ -231,10 +242,10 @@ class CaSE(nn.Module):
         handed up one layer, beyond the reference's interface: a caller with a stream of its own (antithetic or common random numbers across
         models, a replayed draw) supplies u of row b N + n at step t as uniforms[t, b N + n]; it replaces ``seed`` and the counter generator."""
         sampling = sampling_params(self.vocab2id, num_samples, temperature, top_k, top_p, seed, uniforms)
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling)
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram))
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
-    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, **sampling):
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, **sampling):
         """Consensus (minimum-Bayes-risk) selection under ROUGE-L (eval mode only): the answer is the candidate of a pool with the highest
         expected ROUGE-L F against the pool, instead of the pool's slot 0.  ``pool="sample"``: ``do_sample`` with ``self.sampling`` overridden
         by ``**sampling`` (``num_samples`` defaults to ``self.consensus_samples``); ``pool="beam"``: ``do_beam`` (``width=`` may be given), the
@@ -243,7 +254,8 @@ class CaSE(nn.Module):
         exp(-length x ``sample_scores``)) as in ``evaluation.consensus``.  N <= 64, T <= 256, ids < 2^31; an empty candidate counts as [UNK].
         -> the pool's dict with ``answer`` [B, T] replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility`` [B, N] (-inf where
         invalid) and ``pairwise_f`` [B, N, N].  Nothing is read back: with a sample pool at an integer ``seed`` the pass captures into one graph."""
-        return consensus_answers(self, data, lambda d: self._encode_select_extract(d)[2][0], pool, candidates, valid, weights, **sampling)
+        return consensus_answers(self, data, lambda d: self._encode_select_extract(d)[2][0], pool, candidates, valid, weights,
+                                 no_repeat_ngram=no_repeat_ngram, **sampling)
 
     def do_score(self, data, answers=None):
         """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at

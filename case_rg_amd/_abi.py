@@ -17,7 +17,7 @@ F32, BF16 = 0, 1
 WS_ATTENTION_SPLITKV, WS_ATTENTION_BWD, WS_OPTIM_SUMSQ, WS_ENCODER_CHAIN_PACK, WS_GEMM_DW_SLABS = 1, 2, 3, 4, 5
 (FEAT_GEMM_256, FEAT_GEMM_SMALL, FEAT_ENCODER_CHAIN, FEAT_ATTN_SCORES, FEAT_ATTN_DECODE, FEAT_OPTIM, FEAT_ATTN_RESIDENT, FEAT_RESERVED_CUS,
  FEAT_GEMM_DW_SLABS, FEAT_DECODER_CHAIN, FEAT_ATTN_DECODE_MQA, FEAT_POINTER_DECODE, FEAT_POINTER_HEAD, FEAT_GEMM_LN, FEAT_STEP_STATE,
- FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS) = (1 << i for i in range(22))
+ FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS, FEAT_NGRAM_BAN) = (1 << i for i in range(23))
 EPI_BIAS_COL, EPI_BIAS_ROW, EPI_GELU, EPI_RELU = 1, 2, 4, 8
 EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ATOMIC, EPI_DROPOUT = 16, 32, 64, 128, 256
 
@@ -127,6 +127,13 @@ SIGNATURES = {
     "case_pointer_head_sample": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32, ptr],
     "case_pointer_head_score": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64, ptr, ptr, i64, i64, i64, ptr],
     "case_beam_advance": [ptr] * 12 + [i64, i64, i64, i32, i64, ptr],
+    "case_pointer_head_decode_ban": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr, i64, i64, i32, i64, ptr],
+    "case_pointer_head_beam_ban": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, i32, ptr, i64, i64, i32, i64, ptr],
+    "case_pointer_head_sample_ban": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32,
+                                     ptr, i64, i64, i32, ptr],
+    "case_beam_advance_ban": [ptr] * 12 + [i64, i64, i64, i32, i64, ptr, ptr, i64, ptr],
+    "case_ngram_ban": [ptr, ptr, ptr, i64, i64, i64, i64, i32, i64, ptr],
+    "case_remove_duplicate_ids": [ptr, ptr, i64, i64, i32, i64, ptr],
     "case_beam_gather": [ptr, ptr, i32, ptr, ptr, ptr, i64, i32, i64, i64, i64, ptr],
     "case_beam_backtrack": [ptr] * 8 + [i64, i32, i64, ptr],
     "case_lcs_pairs": [ptr] * 6 + [i64, i64, i64, i64, i64, ptr],

@@ -270,11 +270,12 @@ class CumulativeTrainer(object):
         nll = float(total) / int(tokens)  # (the one read-back of the evaluation)
         return dict(nll=nll, perplexity=math.exp(nll), tokens=int(tokens))
 
-    def evaluate_rouge(self, dataset, collate_fn, batch_size, method='test', references='response'):
+    def evaluate_rouge(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False):
         """ROUGE-L of ``model(data, method)['answer']`` against ``data[references]`` (int64 [B, T'] or [B, M, T'], all-PAD rows = no ground truth
         there) without building a Python string: ``evaluation.eval_rouge_l_ids`` per batch, the sum kept on the device, one read-back at the
         end -> dict(rouge_l = the mean of the per-item best F x 100 rounded to 2 decimals -- ``evaluation.eval_rouge_l``'s number for
-        ``predict`` + ``to_sentence`` --, items = the items counted).  One process, under no_grad in eval mode; the model's mode is restored
+        ``predict`` + ``to_sentence`` --, items = the items counted).  ``remove_duplicates``: the answers go through the reference's
+        ``remove_duplicate`` on the device first (K33): the number ``Run_Evaluation`` prints for ``save_result``'s answers.  One process, under no_grad in eval mode; the model's mode is restored
         afterwards."""
         from ..evaluation.rouge_ids import eval_rouge_l_ids, model_specials
         was_training = self.model.training
@@ -287,7 +288,7 @@ class CumulativeTrainer(object):
                                                      pin_memory=torch.cuda.is_available())
                 for data in DevicePrefetcher(loader):
                     out = self.model(data, method=method)
-                    part = eval_rouge_l_ids(out['answer'], data[references], specials).sum()
+                    part = eval_rouge_l_ids(out['answer'], data[references], specials, remove_duplicates).sum()
                     total = part if total is None else total + part
                     items += out['answer'].shape[0]
         finally:

@@ -10,6 +10,7 @@ Differences from the reference that do not change results:
   * greedy decoding keeps the reference's step semantics (argmax of the last position, lowest index on ties, fixed
     T steps) but projects each memory's K/V and additive-attention keys once instead of once per step.
 """
+import operator
 import os
 
 import torch
@@ -110,12 +111,31 @@ def sampling_params(vocab2id, num_samples=1, temperature=1.0, top_k=0, top_p=1.0
                 eos=vocab2id[EOS_WORD], unk=vocab2id[UNK_WORD], pad=vocab2id[PAD_WORD])
 
 
+def no_repeat_ngram_param(n, max_target_length=None):
+    """The checked ``no_repeat_ngram`` of the decoders and the task models: an integer >= 0 (0 = off).  With the ban on, a pass is limited to
+    ``ops.NGRAM_MAX_T`` steps (K32 stages a row's history in LDS beside the vocabulary row).  n > max_target_length is legal and bans nothing."""
+    try:
+        n = None if isinstance(n, bool) else operator.index(n)
+    except TypeError:
+        n = None
+    if n is None or n < 0:
+        raise ValueError("no_repeat_ngram must be an integer >= 0 (0 = off)")
+    if n and max_target_length is not None and max_target_length > ops.NGRAM_MAX_T:
+        raise ValueError("no_repeat_ngram: the ban covers passes of up to %d steps (max_target_length %d)" % (ops.NGRAM_MAX_T, max_target_length))
+    return n
+
+
 class _DecodeMode:
     """What differs between the decoding modes of ``PointerDecoderCore._decode``: how a step's head becomes the next ids [R, 1]
     (``fused_step`` from the f32 logits, mixing logits, sorted source map and copy weights [R, len_k]; ``unfused_step`` from the unfused
     ``gen`` / ``dist``), what happens between two steps, when the pass may end early and what it returns.  The rows of one item are
     consecutive: row b * N + n is candidate n (beam slot, sample) of item b."""
     counter = None  # the decoder attribute that receives the number of steps the pass ran: last_greedy_steps / last_beam_steps / last_sample_steps
+    ngram = 0  # no_repeat_ngram (K32): 0 = off, the launches of a pass without it
+
+    def _banned_copy(self, dist, hist, t, eos):
+        """The unfused head with the ban on: a float copy of the newest position's distribution with the banned entries zeroed."""
+        return ops.ngram_ban_(dist[:, -1].detach().to(torch.float32, copy=True), hist, t, self.ngram, eos)
 
     def start(self, capturing, self_kvs, hist_valid):
         pass
@@ -134,8 +154,9 @@ class _GreedyMode(_DecodeMode):
     the last one.  -> (dec_out, gen, dist of the last step, answer [B, T], PAD behind a short pass)."""
     counter = "last_greedy_steps"
 
-    def __init__(self, decoder, B, T, dev):
-        self.T, self.V, self.eos = T, decoder.tgt_vocab_size, decoder.eos_id
+    def __init__(self, decoder, B, T, dev, ngram=0):
+        self.T, self.V, self.eos, self.ngram = T, decoder.tgt_vocab_size, decoder.eos_id, ngram
+        self.hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if ngram else None  # K23 appends its argmax at [:, t]
         self.finished = None if self.eos is None else torch.zeros(B, dtype=torch.bool, device=dev)
         self.picked, self.gen, self.dist = [], None, None
 
@@ -144,11 +165,18 @@ class _GreedyMode(_DecodeMode):
 
     def fused_step(self, t, logits, mix_logits, source_map, copies):
         want = t == self.T - 1 or self.any_step_may_be_last
-        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want)
+        ban = (self.hist, t, self.ngram, self.eos) if self.ngram else None
+        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want, ban=ban)
         self.gen, self.dist = (gen.view(-1, 1, self.V), dist.view(-1, 1, self.V)) if want else (None, None)
         return self._emit(ids.unsqueeze(1))
 
     def unfused_step(self, t, gen, dist):
+        if self.ngram:  # dist is returned as the row after the ban, as K23 returns it
+            row = self._banned_copy(dist, self.hist, t, self.eos)
+            ids = ops.row_argmax(row)[0]
+            self.hist[:, t] = ids
+            self.gen, self.dist = gen, row.unsqueeze(1)
+            return self._emit(ids.unsqueeze(1))
         self.gen, self.dist = gen, dist
         return self._emit(ops.row_argmax(dist[:, -1])[0].unsqueeze(1))
 
@@ -178,9 +206,9 @@ class _BeamMode(_DecodeMode):
     slot is alive.  -> (dec_out of the last step's rows, None, None, answer [B, T], beam_answers [B, W, T], beam_scores [B, W])."""
     counter = "last_beam_steps"
 
-    def __init__(self, decoder, B, W, T, dev):
-        self.W, self.eos = W, decoder.beam_eos_id
-        self.state = ops.BeamState(B, W, T, dev)
+    def __init__(self, decoder, B, W, T, dev, ngram=0):
+        self.W, self.eos, self.ngram = W, decoder.beam_eos_id, ngram
+        self.state = ops.BeamState(B, W, T, dev, flat=bool(ngram))  # the flat history: a slot's history is its hypothesis, K25 carries it along
 
     def start(self, capturing, self_kvs, hist_valid):
         spare = [[torch.zeros_like(c) for c in layers] for layers in self_kvs]
@@ -188,11 +216,13 @@ class _BeamMode(_DecodeMode):
         self.spare = (spare, torch.zeros_like(hist_valid), [c for layers in spare for c in layers])
 
     def fused_step(self, t, logits, mix_logits, source_map, copies):
-        _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W)
+        ban = (self.state.flat_rows(t), t, self.ngram, self.eos) if self.ngram else None
+        _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W, ban=ban)
         return self._advance(t, cand_p, cand_id)
 
     def unfused_step(self, t, gen, dist):
-        return self._advance(t, *torch.topk(dist[:, -1].detach().float(), self.W, dim=-1))
+        row = self._banned_copy(dist, self.state.flat_rows(t), t, self.eos) if self.ngram else dist[:, -1].detach().float()
+        return self._advance(t, *torch.topk(row, self.W, dim=-1))
 
     def _advance(self, t, cand_p, cand_id):
         ops.beam_advance(self.state, cand_p, cand_id, t, self.eos)
@@ -226,8 +256,10 @@ class _SampleMode(_DecodeMode):
     -> (dec_out of the last step's rows, None, None, answer [B, T], samples [B, N, T], sample_probs [B, N, T], sample_scores [B, N])."""
     counter = "last_sample_steps"
 
-    def __init__(self, B, T, dev, params):
+    def __init__(self, B, T, dev, params, ngram=0):
         self.B, self.N, self.T, self.R, self.pad = B, int(params["num_samples"]), T, B * int(params["num_samples"]), params["pad"]
+        self.ngram = ngram
+        self.hist = torch.zeros(self.R, T, dtype=torch.int32, device=dev) if ngram else None  # K28 appends the emitted id at [:, t]
         self.seed, self.uniforms = params.get("seed"), params.get("uniforms")
         if self.uniforms is not None and tuple(self.uniforms.shape) != (T, self.R):
             raise ValueError("sampled decoding: uniforms must be [max_target_length, batch * num_samples] = [%d, %d]" % (T, self.R))
@@ -238,6 +270,8 @@ class _SampleMode(_DecodeMode):
     def _draw(self, t, *head, **kw):
         u = None if self.uniforms is None else self.uniforms[t]
         rng = None if u is not None else config.next_rng(self.R) if self.seed is None else (int(self.seed), t * self.R, None)
+        if self.ngram:  # (K28 applies the ban to either row source, the unfused ``dist_in`` included)
+            kw["ban"] = (self.hist, t, self.ngram)
         _, _, tok, p = ops.pointer_head_sample(*head, self.ended, t == 0, t == self.T - 1, *self.draw, rng=rng, uniforms=u, **kw)
         self.picked.append(tok.unsqueeze(1))
         self.probs.append(p.unsqueeze(1))
@@ -486,9 +520,9 @@ class PointerDecoderCore(nn.Module):
         return dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
 
     def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-             score_index, feature_of=None):
+             score_index, feature_of=None, no_repeat_ngram=0):
         """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
-        (CaSE's answer representation), or None."""
+        (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) applies to the three decoding modes only."""
         B, dev = source_map.size(0), encode_memories[0].device
         source_map = self._sorted(source_map)
         mems = [m.reshape(B, -1, self.hidden_size) for m in encode_memories]
@@ -505,18 +539,21 @@ class PointerDecoderCore(nn.Module):
         if self.training:
             return None
         feat = None if feature_of is None else feature_of(1)
+        ngram = no_repeat_ngram_param(no_repeat_ngram, T)
+        if ngram and not ops.ngram_ban_supported():
+            raise RuntimeError("no_repeat_ngram: this build of the library lacks the n-gram ban (CASE_FEAT_NGRAM_BAN)")
         if beam_width:
             W = int(beam_width)
             if not ops.beam_supported(W):
                 raise RuntimeError("beam search: width %d is outside what the beam kernels are built for (1 .. 8)" % W)
-            mode, n = _BeamMode(self, B, W, T, dev), W
+            mode, n = _BeamMode(self, B, W, T, dev, ngram), W
         elif sampling:
             if not ops.sample_supported(self.tgt_vocab_size):
                 raise RuntimeError("sampled decoding: the vocabulary (%d) is beyond what the sampling kernel holds in LDS (V <= 36000)"
                                    % self.tgt_vocab_size)
-            mode, n = _SampleMode(B, T, dev, sampling), int(sampling["num_samples"])
+            mode, n = _SampleMode(B, T, dev, sampling, ngram), int(sampling["num_samples"])
         else:
-            mode, n = _GreedyMode(self, B, T, dev), 1
+            mode, n = _GreedyMode(self, B, T, dev, ngram), 1
         # beam search repeats its rows at width 1 too
         return self._decode(mode, *self._per_item(n, mems, valid, weights, source_map, feat, unit_too=bool(beam_width)), BOS, T)
 
@@ -584,8 +621,9 @@ class TransformerSeqDecoder(PointerDecoderCore):
         return dec_out, torch.cat([dec_in, dec_out], dim=-1)
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
-                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None):
+                groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
+                no_repeat_ngram=0):
         if isinstance(source_maps, (list, tuple)):
             source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
         return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index)
+                         score_index, no_repeat_ngram=no_repeat_ngram)

@@ -141,3 +141,22 @@ def remove_duplicate_once(sents, n=3):
 def remove_duplicate(sents, n=3):
     while remove_duplicate_once(sents, n):
         pass
+
+
+def remove_duplicate_ids(ids, len, n=3, pad=0):
+    """``remove_duplicate`` on the device (K33), in place on ``sentence_compact``'s outputs: ids int64 [B, T] front-packed, len int32 [B]
+    -> (ids, len) with every row truncated as ``remove_duplicate`` truncates its token list and PAD behind the new length.  T <= 256."""
+    return ops.remove_duplicate_ids(ids, len, n, pad)
+
+
+def banned_tokens(history, n, vocab_size=None, eos=None):
+    """The n-gram ban (K32) restated on a Python list: ``history`` = the ids a row has emitted so far (BOS excluded), t = len(history).
+    -> the sorted ids v such that some j <= t - n has history[j : j + n - 1] == history[t - n + 1 : t] and history[j + n - 1] == v; for
+    n = 1 every id of the history.  Empty for n < 1, t < n, or a history that holds ``eos``; ids outside [0, vocab_size) are left out."""
+    history = [int(x) for x in history]
+    t = len(history)
+    if n < 1 or t < n or (eos is not None and eos in history):
+        return []
+    suffix = history[t - n + 1:t]
+    banned = {history[j + n - 1] for j in range(t - n + 1) if history[j:j + n - 1] == suffix}
+    return sorted(v for v in banned if v >= 0 and (vocab_size is None or v < vocab_size))

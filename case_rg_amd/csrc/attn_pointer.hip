@@ -478,6 +478,41 @@ struct HeadArgs {
   int nmem;
 };
 
+// ---- K32: the n-gram ban behind the row build ------------------------------------------------------------------------------------------
+// hist [R, Tmax] int32 holds what a row has emitted so far (BOS excluded); at step t with n = no_repeat_ngram, token v is banned when some
+// j <= t - n has hist[j .. j + n - 2] == hist[t - n + 1 .. t - 1] and hist[j + n - 1] == v (n = 1: every token of the history).  A banned
+// entry of the row becomes 0.0; nothing else changes and nothing is renormalised.  No ban for t < n, for a history that holds `eos`, or (the
+// caller's check) for a sampler row that has ended.  Ids outside [0, V) are ignored.  The history is staged in `stage` (t <= NB_MAX_T ints:
+// the value half of the key staging, dead behind the row build); thread j owns window j; several threads may write the same 0.0.
+constexpr int NB_MAX_T = 256;
+struct BanArgs {
+  int32_t* hist;         // [R, Tmax]; K23 / K28 append their emitted id at [r, t]
+  int64_t Tmax, eos;
+  int t, n;
+};
+
+// Every thread of the block calls it; `row` is readable by every thread before and after (barriers inside).
+__device__ __forceinline__ void ngram_ban_row(float* row, const int64_t V, const int32_t* __restrict__ h, const int t, const int n, const int64_t eos,
+                                              int* stage) {
+  if (n < 1 || t < n || t > NB_MAX_T) return;  // (block-uniform)
+  const int tid = threadIdx.x, nt = blockDim.x;
+  int has_eos = 0;
+  for (int i = tid; i < t; i += nt) {
+    const int x = h[i];
+    stage[i] = x;
+    has_eos |= (int64_t)x == eos;
+  }
+  if (__syncthreads_or(has_eos)) return;  // (the barrier that publishes the staged history)
+  const int s0 = t - n + 1;               // the suffix hist[s0 .. t - 1]: n - 1 tokens
+  for (int j = tid; j <= t - n; j += nt) {
+    bool same = true;
+    for (int k = 0; k < n - 1; ++k) same = same && stage[j + k] == stage[s0 + k];
+    const int v = stage[j + n - 1];
+    if (same && v >= 0 && (int64_t)v < V) row[v] = 0.f;
+  }
+  __syncthreads();
+}
+
 // the row build shared by K23 and its beam form: row[0 .. V) = pm_0 softmax(logits) + the pointer mass of the sorted source keys (gen written
 // on the way when asked for).  Ends behind a barrier: every thread may read the whole row.
 __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float* row, uint32_t* tk, float* tv, float* red, const int64_t b) {
@@ -559,7 +594,8 @@ __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float*
   }
 }
 
-__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a) {
+template <bool BAN>
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   float* row = ph_smem;                                  // [V]
   uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
@@ -570,6 +606,7 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
   const int64_t b = blockIdx.x, V = a.V;
   const int tid = threadIdx.x;
   pointer_head_build_row(a, row, tk, tv, red, b);
+  if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));
   // outputs: the distribution row and its argmax (lowest index on ties)
   float bv = -INFINITY;
   int64_t bi = V;
@@ -603,6 +640,7 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
       }
     a.ids[b] = bi < V ? bi : 0;
     if (a.top) a.top[b] = bv;
+    if constexpr (BAN) nb.hist[b * nb.Tmax + nb.t] = (int32_t)(bi < V ? bi : 0);
   }
 }
 
@@ -612,8 +650,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
 // W largest entries with the lowest id first on ties, whatever the scheduling; round 0 is K23's argmax comparison for comparison, so W = 1
 // returns K23's id and value bit for bit.  Scratch on top of K23's: two words for the previous winner.
 constexpr int PH_MAX_W = 8;
+template <bool BAN>
 __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const HeadArgs a, float* __restrict__ cand_p, int64_t* __restrict__ cand_id,
-                                                                       const int W) {
+                                                                       const int W, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   float* row = ph_smem;
   uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
@@ -626,6 +665,7 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const Hea
   const int64_t b = blockIdx.x, V = a.V;
   const int tid = threadIdx.x;
   pointer_head_build_row(a, row, tk, tv, red, b);
+  if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));  // (K25 appends: a slot's history is its hypothesis)
   float pv = INFINITY;  // the previous round's winner: round 0 admits every entry
   int64_t pi = -1;
   for (int r = 0; r < W; ++r) {
@@ -880,7 +920,8 @@ __device__ __forceinline__ float sample_scan64(float x, int lane) {  // inclusiv
   return x;
 }
 
-__global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s) {
+template <bool BAN>
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   float* row = ph_smem;
   uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
@@ -899,6 +940,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
   } else {
     for (int i = tid; i < V; i += PH_THREADS) row[i] = s.dist_in[b * a.V + i];
     __syncthreads();
+  }
+  if constexpr (BAN) {
+    if (!s.ended[b]) ngram_ban_row(row, a.V, nb.hist + b * nb.Tmax, nb.t, nb.n, s.eos, reinterpret_cast<int*>(tv));  // (block-uniform; tid 0 rewrites ended[b] behind the last barrier)
   }
   float pmax = 0.f;
   for (int i = tid; i < V; i += PH_THREADS) {
@@ -1005,9 +1049,18 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
     else if (s.last) emit = e ? s.pad : s.eos;
     else emit = e ? s.pad : (int64_t)x;
     s.ids[b] = emit;
+    if constexpr (BAN) nb.hist[b * nb.Tmax + nb.t] = (int32_t)emit;
     s.prob[b] = e ? 1.f : row[x];
     s.ended[b] = (uint8_t)(e || this_end);
   }
+}
+
+// K32 on a distribution row in global memory (the unfused head): one wave per row
+__global__ __launch_bounds__(64) void ngram_ban_kernel(float* __restrict__ dist, const uint8_t* __restrict__ ended, const int64_t V, const BanArgs nb) {
+  __shared__ int stage[NB_MAX_T];
+  const int64_t b = blockIdx.x;
+  if (ended && ended[b]) return;
+  ngram_ban_row(dist + b * V, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, stage);
 }
 
 // ---- K29: the head of a teacher-forced SCORING pass: one probability per row, no vocabulary row -------------------------------------------
@@ -1433,52 +1486,103 @@ static int pointer_head_reserve(const void* kernel, bool& done, const char* who)
   return CASE_OK;
 }
 
-extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
-                                        int64_t S, case_stream_t stream) {
-  CASE_REQUIRE(ids, "case_pointer_head_decode: bad argument");
+// the history operands of the `_ban` forms (K32): hist [R, Tmax] int32, step t, n >= 1
+static int pointer_head_ban(BanArgs& nb, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos) {
+  CASE_REQUIRE(hist && n >= 1 && t >= 0 && t < Tmax, "%s: bad history argument", who);
+  if (t > NB_MAX_T) return case_set_error(CASE_E_UNSUPPORTED, "%s: the n-gram ban stages histories of up to %d tokens (step %lld)", who, NB_MAX_T, (long long)t);
+  nb.hist = const_cast<int32_t*>(hist);
+  nb.Tmax = Tmax;
+  nb.eos = eos;
+  nb.t = (int)t;
+  nb.n = (int)n;
+  return CASE_OK;
+}
+
+template <bool BAN>
+static int pointer_head_decode_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                      int64_t S, const BanArgs& nb, case_stream_t stream) {
+  CASE_REQUIRE(ids, "%s: bad argument", who);
   HeadArgs a;
-  int rc = pointer_head_args(a, "case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
+  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
   if (rc != CASE_OK) return rc;
   a.ids = ids;
   a.top = top;
   static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel), attr, "case_pointer_head_decode");
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel<BAN>), attr, who);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_decode_kernel, dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a);
-  return case_check_launch("case_pointer_head_decode");
+  hipLaunchKernelGGL(pointer_head_decode_kernel<BAN>, dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, nb);
+  return case_check_launch(who);
+}
+
+extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                        int64_t S, case_stream_t stream) {
+  return pointer_head_decode_launch<false>("case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S,
+                                           BanArgs(), stream);
+}
+
+extern "C" int case_pointer_head_decode_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                            const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                            int64_t V, int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                            case_stream_t stream) {
+  BanArgs nb;
+  const int rc = pointer_head_ban(nb, "case_pointer_head_decode_ban", hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_decode_launch<true>("case_pointer_head_decode_ban", logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S,
+                                          nb, stream);
+}
+
+template <bool BAN>
+static int pointer_head_beam_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                    const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V,
+                                    int64_t S, int32_t W, const BanArgs& nb, case_stream_t stream) {
+  CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
+  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
+  HeadArgs a;
+  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+  if (rc != CASE_OK) return rc;
+  static bool attr = false;
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel<BAN>), attr, who);
+  if (rc != CASE_OK) return rc;
+  hipLaunchKernelGGL(pointer_head_beam_kernel<BAN>, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id,
+                     (int)W, nb);
+  return case_check_launch(who);
 }
 
 extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                       const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
                                       int64_t V, int64_t S, int32_t W, case_stream_t stream) {
-  CASE_REQUIRE(cand_p && cand_id, "case_pointer_head_beam: bad argument");
-  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_beam: width %d outside 1 .. min(%d, V)", W, PH_MAX_W);
-  HeadArgs a;
-  int rc = pointer_head_args(a, "case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
-  if (rc != CASE_OK) return rc;
-  static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel), attr, "case_pointer_head_beam");
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_beam_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id, (int)W);
-  return case_check_launch("case_pointer_head_beam");
+  return pointer_head_beam_launch<false>("case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W,
+                                         BanArgs(), stream);
 }
 
-extern "C" int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
-                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
-                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
-                                        int64_t pad, int32_t first, int32_t last, case_stream_t stream) {
-  CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "case_pointer_head_sample: bad argument");
-  CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f,
-               "case_pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]");
-  CASE_REQUIRE((logits != nullptr) != (dist_in != nullptr), "case_pointer_head_sample: give either the logits or a ready distribution");
+extern "C" int case_pointer_head_beam_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                          const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                          int64_t V, int64_t S, int32_t W, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                          case_stream_t stream) {
+  BanArgs nb;
+  const int rc = pointer_head_ban(nb, "case_pointer_head_beam_ban", hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_beam_launch<true>("case_pointer_head_beam_ban", logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S,
+                                        W, nb, stream);
+}
+
+template <bool BAN>
+static int pointer_head_sample_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                      const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                      uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                      float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad,
+                                      int32_t first, int32_t last, const BanArgs& nb, case_stream_t stream) {
+  CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "%s: bad argument", who);
+  CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f, "%s: temperature must be > 0, top_k >= 0 and top_p in (0, 1]", who);
+  CASE_REQUIRE((logits != nullptr) != (dist_in != nullptr), "%s: give either the logits or a ready distribution", who);
   HeadArgs a;
   if (logits) {
-    const int rc = pointer_head_args(a, "case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+    const int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
     if (rc != CASE_OK) return rc;
   } else {
-    if (V > PH_MAX_V) return case_set_error(CASE_E_UNSUPPORTED, "case_pointer_head_sample: built for V <= %lld", (long long)PH_MAX_V);
+    if (V > PH_MAX_V) return case_set_error(CASE_E_UNSUPPORTED, "%s: built for V <= %lld", who, (long long)PH_MAX_V);
     a = HeadArgs();
     a.dist = dist;
     a.V = V;
@@ -1501,10 +1605,45 @@ extern "C" int case_pointer_head_sample(const float* logits, const float* mix_lo
   s.first = first;
   s.last = last;
   static bool attr = false;
-  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel), attr, "case_pointer_head_sample");
+  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel<BAN>), attr, who);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_sample_kernel, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s);
-  return case_check_launch("case_pointer_head_sample");
+  hipLaunchKernelGGL(pointer_head_sample_kernel<BAN>, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s, nb);
+  return case_check_launch(who);
+}
+
+extern "C" int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
+                                        int64_t pad, int32_t first, int32_t last, case_stream_t stream) {
+  return pointer_head_sample_launch<false>("case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob,
+                                           ended, uniforms, R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last,
+                                           BanArgs(), stream);
+}
+
+extern "C" int case_pointer_head_sample_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                            const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                            float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
+                                            int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
+                                            int64_t unk, int64_t pad, int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
+                                            case_stream_t stream) {
+  BanArgs nb;
+  const int rc = pointer_head_ban(nb, "case_pointer_head_sample_ban", hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_sample_launch<true>("case_pointer_head_sample_ban", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob,
+                                          ended, uniforms, R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb,
+                                          stream);
+}
+
+// K32 as a launch of its own (the unfused head): one wave per row zeroes the banned entries of dist [R, V] in place
+extern "C" int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n,
+                              int64_t eos, case_stream_t stream) {
+  CASE_REQUIRE(dist && R > 0 && R < (1ll << 31) && V > 0, "case_ngram_ban: bad argument");
+  BanArgs nb;
+  const int rc = pointer_head_ban(nb, "case_ngram_ban", hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  hipLaunchKernelGGL(ngram_ban_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, dist, ended, V, nb);
+  return case_check_launch("case_ngram_ban");
 }
 
 extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
@@ -1592,6 +1731,68 @@ __global__ void sentence_compact_kernel(const int64_t* __restrict__ ids, int64_t
   len[b] = n;
   for (int64_t t = n; t < T; ++t) out[b * T + t] = pad;
 }
+
+// ---- K33: the reference's remove_duplicate (common/Utils.py:170-193) on front-packed ids ------------------------------------------------
+// One pass of remove_duplicate_once cuts a sentence of length L at the LARGEST i in [1, L - n] whose tail [i, L) holds only tokens that also
+// occur in [0, i); the pass repeats until nothing is cut or L <= n.  With first[p] = the first position of token out[p] (unchanged by a cut),
+// "every token of the tail occurs in the prefix" is  g(i) = max_{p >= i} first[p] < i.  One wave per row, T <= 256: lane l owns the four
+// positions 4 l .. 4 l + 3, first[] stays in registers, and a pass is a suffix maximum over the wave (local, then a shuffle scan).
+constexpr int RD_MAX_T = 256;
+__global__ __launch_bounds__(64) void remove_duplicate_kernel(int64_t* __restrict__ out, int32_t* __restrict__ len, const int64_t T, const int n,
+                                                              const int64_t pad) {
+  __shared__ int64_t tok[RD_MAX_T];
+  const int64_t b = blockIdx.x;
+  const int lane = threadIdx.x;
+  int64_t* row = out + b * T;
+  int L = len[b];
+  L = L < 0 ? 0 : (L > (int)T ? (int)T : L);
+  const int L0 = L;
+  for (int i = lane; i < L0; i += 64) tok[i] = row[i];
+  __syncthreads();
+  int first[4];
+#pragma unroll
+  for (int e = 0; e < 4; ++e) {
+    const int p = 4 * lane + e;
+    first[e] = p;
+    if (p < L0) {
+      const int64_t mine = tok[p];
+      for (int q = 0; q < p; ++q)
+        if (tok[q] == mine) {
+          first[e] = q;
+          break;
+        }
+    }
+  }
+  while (L > n) {  // (wave-uniform)
+    int s[4];
+#pragma unroll
+    for (int e = 3; e >= 0; --e) {
+      const int p = 4 * lane + e;
+      const int x = p < L ? first[e] : -1;
+      s[e] = e == 3 ? x : max(x, s[e + 1]);
+    }
+    int tot = s[0];  // the inclusive suffix maximum over the lanes' totals
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int other = __shfl_down(tot, o, 64);
+      if (lane + o < 64) tot = max(tot, other);
+    }
+    int after = __shfl_down(tot, 1, 64);
+    if (lane == 63) after = -1;
+    int best = 0;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      const int i = 4 * lane + e;
+      if (i >= 1 && i <= L - n && max(s[e], after) < i) best = i;  // (i ascends: the lane's largest)
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) best = max(best, __shfl_xor(best, o, 64));
+    if (best < 1) break;
+    L = best;
+  }
+  for (int i = L + lane; i < L0; i += 64) row[i] = pad;
+  if (lane == 0) len[b] = L;
+}
 }  // namespace
 
 extern "C" int case_sentence_compact(const int64_t* ids, int64_t* out, int32_t* len, int64_t B, int64_t T, int64_t bos, int64_t pad,
@@ -1600,6 +1801,13 @@ extern "C" int case_sentence_compact(const int64_t* ids, int64_t* out, int32_t* 
   hipLaunchKernelGGL(sentence_compact_kernel, dim3((unsigned)((B + 63) / 64)), dim3(64), 0, (hipStream_t)stream, ids, out, len, B, T, bos,
                      pad, eos);
   return case_check_launch("case_sentence_compact");
+}
+
+extern "C" int case_remove_duplicate_ids(int64_t* out, int32_t* len, int64_t B, int64_t T, int32_t n, int64_t pad, case_stream_t stream) {
+  CASE_REQUIRE(out && len && B > 0 && B < (1ll << 31) && T > 0 && n >= 1, "case_remove_duplicate_ids: bad argument");
+  if (T > RD_MAX_T) return case_set_error(CASE_E_UNSUPPORTED, "case_remove_duplicate_ids: rows of up to %d positions (got %lld)", RD_MAX_T, (long long)T);
+  hipLaunchKernelGGL(remove_duplicate_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, out, len, T, (int)n, pad);
+  return case_check_launch("case_remove_duplicate_ids");
 }
 
 extern "C" int case_row_argmax(const float* x, int64_t* idx, float* val, int64_t rows, int64_t cols, int64_t ld,

@@ -16,13 +16,21 @@ constexpr int BEAM_MAX_W = 8;
 // One wave per item.  Lane l < W * W holds candidate (parent slot l / W, candidate rank l % W): key = (cum[slot] - log(p + 1e-10)) / (len[slot] + 1),
 // +inf for a dead parent.  A lane's place in the stable ascending order is the number of lanes that come before it (smaller key, or the same
 // key and a lower lane: Python's sorted() over the (parent slot, candidate rank) sequence); places 0 .. W-1 become the new slots.
+// FLAT (K32's beam state): flat_old / flat_new int32 [B, W, Tmax] hold every slot's hypothesis so far, one buffer read and the other written
+// (a copy by parent cannot run in place): new[b, w, 0 .. t) = old[b, parent, 0 .. t), new[b, w, t] = the slot's token -- W t <= 2048 ints per
+// item.  With the ban on, a candidate of probability exactly 0 (a banned entry that reached the top W) is dead: it can neither take a slot nor
+// retire into the pool.
+template <bool FLAT>
 __global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restrict__ cand_p, const int64_t* __restrict__ cand_id,
                                                           uint8_t* __restrict__ alive, float* __restrict__ cum, int32_t* __restrict__ len,
                                                           int32_t* __restrict__ parent, int64_t* __restrict__ token,
                                                           int32_t* __restrict__ hist_parent, int64_t* __restrict__ hist_token,
                                                           float* __restrict__ fin_key, int32_t* __restrict__ fin_step, int32_t* __restrict__ fin_slot,
-                                                          const int t, const int T, const int64_t B, const int W, const int64_t eos) {
+                                                          const int t, const int T, const int64_t B, const int W, const int64_t eos,
+                                                          const int32_t* __restrict__ flat_old, int32_t* __restrict__ flat_new,
+                                                          const int64_t Tmax) {
   __shared__ int src[BEAM_MAX_W];
+  __shared__ int n_par[BEAM_MAX_W], n_tok[BEAM_MAX_W];
   __shared__ float s_key[64], s_cum[64];
   __shared__ int64_t s_tok[64];
   __shared__ int s_len[64];
@@ -39,8 +47,11 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restric
     tok = cand_id[row * W + (lane - slot * W)];
     plen = len[row];
     if (alive[row]) {
-      c = cum[row] - logf(cand_p[row * W + (lane - slot * W)] + 1e-10f);
-      key = c / (float)(plen + 1);
+      const float p = cand_p[row * W + (lane - slot * W)];
+      if (!(FLAT && p == 0.f)) {
+        c = cum[row] - logf(p + 1e-10f);
+        key = c / (float)(plen + 1);
+      }
     }
   }
   if (!(key < INFINITY)) key = INFINITY;  // (a NaN probability counts as a dead candidate)
@@ -75,8 +86,20 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restric
     hist_token[((int64_t)t * B + b) * W + lane] = stok;
     n_key[lane] = live ? s_key[s] : INFINITY;
     n_retire[lane] = retire ? 1 : 0;
+    if constexpr (FLAT) {
+      n_par[lane] = sp;
+      n_tok[lane] = (int)stok;
+    }
   }
   __syncthreads();
+  if constexpr (FLAT) {
+    for (int w = 0; w < W; ++w) {
+      const int32_t* from = flat_old + (b * W + n_par[w]) * Tmax;
+      int32_t* to = flat_new + (b * W + w) * Tmax;
+      for (int i = lane; i < t; i += 64) to[i] = from[i];
+      if (lane == 0) to[t] = n_tok[w];
+    }
+  }
   // the finished pool: ascending by key, a newcomer behind its equals (list.sort is stable over the order of retirement); a key is final
   // when its hypothesis retires, so whatever falls off the end could never have been among the best W
   if (lane == 0) {
@@ -190,9 +213,22 @@ extern "C" int case_beam_advance(const float* cand_p, const int64_t* cand_id, ui
                    B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T,
                "case_beam_advance: bad argument");
   if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance: width %d outside 1 .. %d", W, BEAM_MAX_W);
-  hipLaunchKernelGGL(beam_advance_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
-                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos);
+  hipLaunchKernelGGL(beam_advance_kernel<false>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
+                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, nullptr, nullptr, (int64_t)0);
   return case_check_launch("case_beam_advance");
+}
+
+extern "C" int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
+                                     int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step,
+                                     int32_t* fin_slot, int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, const int32_t* flat_old,
+                                     int32_t* flat_new, int64_t Tmax, case_stream_t stream) {
+  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
+                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T && flat_old && flat_new && flat_old != flat_new && t < Tmax,
+               "case_beam_advance_ban: bad argument");
+  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance_ban: width %d outside 1 .. %d", W, BEAM_MAX_W);
+  hipLaunchKernelGGL(beam_advance_kernel<true>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
+                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax);
+  return case_check_launch("case_beam_advance_ban");
 }
 
 extern "C" int case_beam_gather(const void* const* src, void* const* dst, int32_t nlayers, const int32_t* parent, const uint8_t* valid_src,

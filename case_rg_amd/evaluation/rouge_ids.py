@@ -30,10 +30,12 @@ def _pool(ids, what):
     return ids.unsqueeze(1) if ids.dim() == 2 else ids
 
 
-def rouge_l_ids(hyp, ref, specials):
+def rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
     """hyp int64 [B, T] or [B, N, T], ref int64 [B, T'] or [B, M, T'] (raw ids on the device, as the decoders and the batches hold them),
     specials = (bos, pad, eos, unk) -> dict(lcs int32, f f32, p f64, r f64: all [B, N, M]; ref_valid bool [B, M]).  f / p / r are
-    ``rouge.rouge_l``'s of hypothesis n against reference m; an absent reference (``ref_valid`` False) reads 0 everywhere."""
+    ``rouge.rouge_l``'s of hypothesis n against reference m; an absent reference (``ref_valid`` False) reads 0 everywhere.
+    ``remove_duplicates``: the compacted HYPOTHESES (not the references) go through the reference's ``remove_duplicate`` first (K33), as its
+    ``save_result`` does before an answer is written or evaluated."""
     bos, pad, eos, unk = specials
     hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
     if hyp.shape[0] != ref.shape[0]:
@@ -41,19 +43,22 @@ def rouge_l_ids(hyp, ref, specials):
     if hyp.shape[2] > ops.LCS_MAX_T:
         raise ValueError("rouge_l_ids: hypotheses of up to %d positions (got %d)" % (ops.LCS_MAX_T, hyp.shape[2]))
     a, a_len = _compact(hyp, bos, pad, eos, unk)
+    if remove_duplicates:
+        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
     b, b_len = _compact(ref, bos, pad, eos)
     lcs, f = ops.lcs_pairs(a, a_len, b, b_len)
     n = lcs.double()
     return dict(lcs=lcs, f=f, p=n / a_len.double().unsqueeze(2), r=n / b_len.clamp_min(1).double().unsqueeze(1), ref_valid=b_len.gt(0))
 
 
-def eval_rouge_l_ids(hyp, ref, specials):
+def eval_rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
     """hyp int64 [B, T], ref int64 [B, M, T'] (or [B, T']: one ground truth) -> f64 [B] on the device: per item the best F x 100 over its
     present references (0 for an item without one).  Its mean rounded to 2 decimals is ``rouge.eval_rouge_l``'s number (F is K30's f32
-    rounding of the host's f64 value, so a per-item term is within 1.2e-5 of the host's)."""
+    rounding of the host's f64 value, so a per-item term is within 1.2e-5 of the host's).  ``remove_duplicates`` as in ``rouge_l_ids``: the number
+    for the sentences after ``remove_duplicate``."""
     if hyp.dim() != 2:
         raise TypeError("eval_rouge_l_ids: hyp must be int64 [B, T], one answer per item")
-    out = rouge_l_ids(hyp, ref, specials)
+    out = rouge_l_ids(hyp, ref, specials, remove_duplicates)
     f = out["f"][:, 0].double()
     return torch.where(out["ref_valid"], f, torch.zeros_like(f)).max(dim=1)[0] * 100
 
@@ -83,11 +88,14 @@ def model_specials(vocab2id):
     return tuple(vocab2id[w] for w in (BOS_WORD, PAD_WORD, EOS_WORD, UNK_WORD))
 
 
-def consensus_answers(model, data, rank_of, pool="sample", candidates=None, valid=None, weights=None, **sampling):
+def consensus_answers(model, data, rank_of, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, **sampling):
     """``do_consensus`` of the task models (CaSE, Masque): build the pool with the model's own decoders (or take ``candidates``), then
-    ``consensus``.  ``rank_of(data)``: the model's passage ranking from its encode stages alone."""
+    ``consensus``.  ``rank_of(data)``: the model's passage ranking from its encode stages alone.  ``no_repeat_ngram`` goes to the pool's decoder
+    (None: the model's attribute); explicit candidates are taken as they are."""
     if model.training:
         raise ValueError("do_consensus runs in eval mode: call model.eval() first")
+    if candidates is None and pool in ("sample", "beam"):
+        sampling["no_repeat_ngram"] = no_repeat_ngram
     if candidates is not None:
         if sampling:
             raise TypeError("do_consensus: explicit candidates take no decoding arguments (%s)" % ", ".join(sorted(sampling)))

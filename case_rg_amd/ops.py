@@ -1945,16 +1945,30 @@ def _head_operands(logits, mix_logits, source_map, copies):
     return logits, mix_logits, cs, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, source_map.keys.shape[1]
 
 
-def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True):
+def _ban_operands(ban, rows, who):
+    """``ban`` = (hist int32 [rows, Tmax] contiguous, t, n, eos | None) -> the trailing arguments of a ``_ban`` entry point (K32)."""
+    hist, t, n, eos = ban
+    if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != rows or not hist.is_contiguous():
+        raise TypeError("%s: the history must be a contiguous int32 [%d, Tmax]" % (who, rows))
+    if int(n) < 1 or not 0 <= int(t) < hist.shape[1] or int(t) > NGRAM_MAX_T:
+        raise ValueError("%s: n >= 1 and 0 <= t < min(Tmax, %d + 1) (got n %r, t %r, Tmax %d)" % (who, NGRAM_MAX_T, n, t, hist.shape[1]))
+    return _ptr(hist), hist.shape[1], int(t), int(n), -1 if eos is None else int(eos)
+
+
+def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None):
     """logits f32 [B, V]; mix_logits f32 [B, 1 + nmem]; source_map a SortedSource over the concatenated memories; copies: list of f32
-    [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference)."""
+    [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference).
+    ``ban`` = (hist int32 [B, Tmax], t, n, eos | None): K32, the n-gram ban before the argmax; the kernel appends ids at hist[:, t]."""
     B, V = logits.shape
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_dist else None
     ids = torch.empty(B, dtype=torch.int64, device=logits.device)
-    A.call("case_pointer_head_decode", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S,
-           _stream())
+    head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S)
+    if ban is None:
+        A.call("case_pointer_head_decode", *head, _stream())
+    else:
+        A.call("case_pointer_head_decode_ban", *head, *_ban_operands(ban, B, "pointer_head_decode"), _stream())
     return gen, dist, ids
 
 
@@ -1962,17 +1976,21 @@ def beam_supported(width):
     return 1 <= width <= 8 and bool(A.lib.case_abi_features() & A.FEAT_BEAM_DECODE)
 
 
-def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False):
+def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False, ban=None):
     """K24, ``pointer_head_decode`` with a top-``width`` tail: -> (gen [R, V] | None, dist [R, V] | None, cand_p f32 [R, W], cand_id int64 [R, W]),
-    the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference)."""
+    the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference).  ``ban`` as in
+    ``pointer_head_decode``, but the history is only read: row b * W + w is the hypothesis of slot w, which ``beam_advance`` maintains."""
     R, V = logits.shape
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_dist else None
     cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
     cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
-    A.call("case_pointer_head_beam", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p),
-           _ptr(cand_id), R, V, S, width, _stream())
+    head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, S, width)
+    if ban is None:
+        A.call("case_pointer_head_beam", *head, _stream())
+    else:
+        A.call("case_pointer_head_beam_ban", *head, *_ban_operands(ban, R, "pointer_head_topk"), _stream())
     return gen, dist, cand_p, cand_id
 
 
@@ -1981,14 +1999,16 @@ def sample_supported(V):
 
 
 def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, t_last, eos, unk, pad, temperature, top_k, top_p, rng=None,
-                        uniforms=None, dist_in=None, want_gen=False, want_dist=False):
+                        uniforms=None, dist_in=None, want_gen=False, want_dist=False, ban=None):
     """K28, ``pointer_head_decode`` with a draw instead of the argmax: -> (gen [R, V] | None, dist [R, V] | None, ids int64 [R], prob f32 [R]).
     One token per row is drawn from the mixed distribution after temperature, top-k and top-p (the rule: include/case_hip.h); ``ids`` is what
     the reference's ``sample`` loop emits for it (UNK for EOS at the first step, EOS at the last, PAD behind the end) and ``ended`` (uint8 [R])
     is updated in place; ``prob`` is the row's unfiltered probability of the drawn token, 1 for a row that had ended.  The uniform of row r is
     ``uniforms[r]`` (f32 [R]) when given, else the 24-bit counter uniform of ``rng = (seed, offset, state)`` (what ``config.next_rng(R)`` returns)
     at counter ``rng_base + offset + r``.  ``dist_in`` f32 [R, V] with ``logits=None`` draws from a ready distribution instead of building the row
-    (``mix_logits`` / ``source_map`` / ``copies`` unused).  No autograd (inference)."""
+    (``mix_logits`` / ``source_map`` / ``copies`` unused).  ``ban`` = (hist int32 [R, Tmax], t, n): K32, the n-gram ban before pmax, the cuts and
+    the draw (either row source; no ban for a row that has ended or whose history holds ``eos``); the kernel appends ``ids`` at hist[:, t].
+    No autograd (inference)."""
     if not (float(temperature) > 0.0) or int(top_k) < 0 or not (0.0 < float(top_p) <= 1.0):
         raise ValueError("pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]")
     if (logits is None) == (dist_in is None):
@@ -2014,12 +2034,16 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     prob = torch.empty(R, dtype=torch.float32, device=dev)
     tail = (_ptr(gen), _ptr(dist), _ptr(ids), _ptr(prob), _ptr(ended), _ptr(uniforms), R, V)
     draw = (float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), int(seed), int(offset), state, int(eos), int(unk), int(pad),
-            int(bool(t_first)), int(bool(t_last)), _stream())
+            int(bool(t_first)), int(bool(t_last)))
+    if ban is None:
+        entry, draw = "case_pointer_head_sample", draw + (_stream(),)
+    else:
+        entry, draw = "case_pointer_head_sample_ban", draw + _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4] + (_stream(),)
     if logits is None:
-        A.call("case_pointer_head_sample", None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw)
+        A.call(entry, None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw)
     else:
         src, mix_logits, cs, ptrs, lens, n, S = _head_operands(src, mix_logits, source_map, copies)
-        A.call("case_pointer_head_sample", _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, None, *tail, S, *draw)
+        A.call(entry, _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, None, *tail, S, *draw)
     return gen, dist, ids, prob
 
 
@@ -2061,12 +2085,54 @@ def pointer_head_score(logits, mix_logits, source_map, rows_per_source, copies, 
     return prob, copy
 
 
+# K32: the n-gram ban.  The fused heads apply it behind their row build (``ban=`` above); ``ngram_ban_`` is the same rule as a launch of its own.
+NGRAM_MAX_T = 256  # a history is staged in LDS beside the vocabulary row
+
+
+def ngram_ban_supported():
+    return bool(A.lib.case_abi_features() & A.FEAT_NGRAM_BAN)
+
+
+def ngram_ban_(dist, hist, t, n, eos=None, ended=None):
+    """K32 in place on dist f32 [R, V] (contiguous): at step ``t`` with the histories hist int32 [R, Tmax] (BOS excluded), entry v of row r
+    becomes 0.0 when some j <= t - n has hist[r, j : j + n - 1] == hist[r, t - n + 1 : t] and hist[r, j + n - 1] == v.  Nothing else changes
+    (no renormalisation).  No ban for t < n, a history that holds ``eos``, or a row with ``ended`` (uint8 [R]) set.  -> dist."""
+    if dist.dtype != torch.float32 or dist.dim() != 2 or not dist.is_contiguous():
+        raise TypeError("ngram_ban_: dist must be a contiguous f32 [R, V]")
+    R, V = dist.shape
+    if ended is not None and (ended.dtype != torch.uint8 or tuple(ended.shape) != (R,) or not ended.is_contiguous()):
+        raise TypeError("ngram_ban_: ended must be a contiguous uint8 [R]")
+    hp, Tmax, t, n, eos = _ban_operands((hist, t, n, eos), R, "ngram_ban_")
+    A.call("case_ngram_ban", _ptr(dist), hp, _ptr(ended), R, V, Tmax, t, n, eos, _stream())
+    return dist
+
+
+def remove_duplicate_ids(out, len, n=3, pad=0):
+    """K33: the reference's ``remove_duplicate`` on ``sentence_compact``'s outputs, in place: out int64 [B, T] front-packed ids, len int32 [B].
+    Per row, while the length L > n: cut at the largest i in [1, L - n] whose tail out[i:L] holds only tokens of out[:i].  PAD behind the new
+    length, ``len`` updated.  T <= 256.  -> (out, len)."""
+    if out.dtype != torch.int64 or out.dim() != 2 or not out.is_contiguous():
+        raise TypeError("remove_duplicate_ids: out must be a contiguous int64 [B, T]")
+    B, T = out.shape
+    if len.dtype != torch.int32 or tuple(len.shape) != (B,) or not len.is_contiguous():
+        raise TypeError("remove_duplicate_ids: len must be a contiguous int32 [B]")
+    if int(n) != n or n < 1:
+        raise ValueError("remove_duplicate_ids: n must be an integer >= 1, not %r" % (n,))
+    if T > NGRAM_MAX_T:
+        raise ValueError("remove_duplicate_ids: rows of up to %d positions (got %d)" % (NGRAM_MAX_T, T))
+    A.call("case_remove_duplicate_ids", _ptr(out), _ptr(len), B, T, int(n), int(pad), _stream())
+    return out, len
+
+
 class BeamState(object):
     """The device-side state of one beam-search pass over B items x W slots and at most T steps: what K25 rewrites every step (``parent``,
-    ``token``, ``cum``, ``len``, ``alive``), the [T, B, W] history K27 walks back, and the finished pool (best W retired hypotheses per item)."""
+    ``token``, ``cum``, ``len``, ``alive``), the [T, B, W] history K27 walks back, and the finished pool (best W retired hypotheses per item).
+    ``flat=True`` adds the flat history of the n-gram ban (K32): int32 [2, B, W, T], every slot's hypothesis so far; step t reads buffer t % 2
+    (``flat_rows(t)``: what K24 takes) and K25 writes buffer (t + 1) % 2."""
 
-    def __init__(self, B, W, T, device):
+    def __init__(self, B, W, T, device, flat=False):
         self.B, self.W, self.T = B, W, T
+        self.flat = torch.zeros(2, B, W, T, dtype=torch.int32, device=device) if flat else None
         self.alive = torch.zeros(B, W, dtype=torch.uint8, device=device)
         self.alive[:, 0] = 1  # the root: BOS in slot 0, cost 0, length 1
         self.cum = torch.zeros(B, W, dtype=torch.float32, device=device)
@@ -2080,16 +2146,26 @@ class BeamState(object):
         self.fin_slot = torch.zeros(B, W, dtype=torch.int32, device=device)
 
 
+    def flat_rows(self, t):
+        """The hypotheses the rows of step ``t`` continue: int32 [B * W, T], positions 0 .. t - 1 filled."""
+        return self.flat[t % 2].view(self.B * self.W, self.T)
+
+
 def beam_advance(state, cand_p, cand_id, t, eos):
-    """K25: step ``t`` of the search on ``state`` (in place) from the candidates cand_p f32 / cand_id int64 [B * W, W] of the step's rows."""
+    """K25: step ``t`` of the search on ``state`` (in place) from the candidates cand_p f32 / cand_id int64 [B * W, W] of the step's rows.  A state
+    with the flat history gets it advanced in the same launch (and there a candidate of probability 0, a banned entry, is dead)."""
     B, W = state.B, state.W
     if tuple(cand_p.shape) != (B * W, W) or tuple(cand_id.shape) != (B * W, W) or cand_p.dtype != torch.float32 or cand_id.dtype != torch.int64:
         raise TypeError("beam_advance: candidates must be f32 / int64 [B * W, W]")
     cand_p = cand_p if cand_p.is_contiguous() else cand_p.contiguous()
     cand_id = cand_id if cand_id.is_contiguous() else cand_id.contiguous()
-    A.call("case_beam_advance", _ptr(cand_p), _ptr(cand_id), _ptr(state.alive), _ptr(state.cum), _ptr(state.len), _ptr(state.parent), _ptr(state.token),
-           _ptr(state.hist_parent), _ptr(state.hist_token), _ptr(state.fin_key), _ptr(state.fin_step), _ptr(state.fin_slot), t, state.T, B, W,
-           -1 if eos is None else eos, _stream())
+    args = (_ptr(cand_p), _ptr(cand_id), _ptr(state.alive), _ptr(state.cum), _ptr(state.len), _ptr(state.parent), _ptr(state.token),
+            _ptr(state.hist_parent), _ptr(state.hist_token), _ptr(state.fin_key), _ptr(state.fin_step), _ptr(state.fin_slot), t, state.T, B, W,
+            -1 if eos is None else eos)
+    if state.flat is None:
+        A.call("case_beam_advance", *args, _stream())
+    else:
+        A.call("case_beam_advance_ban", *args, _ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T, _stream())
 
 
 def beam_gather(src, dst, parent, t, valid_src=None, valid_dst=None):

@@ -74,7 +74,8 @@ enum {
   CASE_FEAT_BEAM_DECODE = 1u << 18,       /* K24-K27 case_pointer_head_beam / case_beam_advance / case_beam_gather / case_beam_backtrack */
   CASE_FEAT_SAMPLE_DECODE = 1u << 19,     /* K28 case_pointer_head_sample */
   CASE_FEAT_POINTER_SCORE = 1u << 20,     /* K29 case_pointer_head_score */
-  CASE_FEAT_CONSENSUS = 1u << 21          /* K30 / K31 case_lcs_pairs / case_consensus_pick */
+  CASE_FEAT_CONSENSUS = 1u << 21,         /* K30 / K31 case_lcs_pairs / case_consensus_pick */
+  CASE_FEAT_NGRAM_BAN = 1u << 22          /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -542,6 +543,35 @@ int case_pointer_head_sample(const float* logits, const float* mix_logits, const
                              const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k, float top_p, uint64_t seed,
                              uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
                              case_stream_t stream);
+/* K32, the n-gram ban (CASE_FEAT_NGRAM_BAN; purely additive, generation 600 unchanged).  hist [R, Tmax] int32 holds what every row has emitted
+ * so far, BOS excluded.  At step t (0 <= t < Tmax, t <= 256) with n >= 1, token v of row r is banned when some j <= t - n has
+ * hist[r, j .. j + n - 2] == hist[r, t - n + 1 .. t - 1] and hist[r, j + n - 1] == v (n = 1: every token of the history).  A banned entry of the
+ * mixed distribution row is set to 0.0 BEFORE the selection (argmax, top-W, pmax / cuts / draw); nothing else changes and the row is not
+ * renormalised, so top / cand_p / prob stay the model's own probabilities and a returned dist is the row after the ban.  No ban for t < n, for a
+ * history that holds `eos` (-1: none), or for a sampler row with ended[r] != 0; ids outside [0, V) in a history are ignored.
+ * case_pointer_head_decode_ban / _sample_ban: the K23 / K28 arguments, then hist, Tmax, t, n (and eos for K23; K28 uses its own); the kernel
+ *   APPENDS the id it emits (K23: the argmax; K28: ids[r] after the first / last / ended conventions) at hist[r, t].
+ * case_pointer_head_beam_ban: K24 likewise; it only reads hist (row b * W + w = the hypothesis of slot w), case_beam_advance_ban appends.
+ * case_beam_advance_ban: K25 with the flat history: flat_old / flat_new int32 [B, W, Tmax], two different buffers;
+ *   flat_new[b, w, 0 .. t) = flat_old[b, parent[b, w], 0 .. t), flat_new[b, w, t] = the slot's token (hist_token's).  A candidate of probability
+ *   exactly 0 is dead here (it takes no slot and does not retire).
+ * case_ngram_ban: the same rule on dist f32 [R, V] in place (one wave per row; ended u8 [R] nullable); it appends nothing. */
+int case_pointer_head_decode_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                 const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                 int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos, case_stream_t stream);
+int case_pointer_head_beam_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                               int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W,
+                               const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos, case_stream_t stream);
+int case_pointer_head_sample_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                                 int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob, uint8_t* ended,
+                                 const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                 uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
+                                 int32_t* hist, int64_t Tmax, int64_t t, int32_t n, case_stream_t stream);
+int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent, int64_t* token,
+                          int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step, int32_t* fin_slot, int64_t t, int64_t T,
+                          int64_t B, int32_t W, int64_t eos, const int32_t* flat_old, int32_t* flat_new, int64_t Tmax, case_stream_t stream);
+int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                   case_stream_t stream);
 /* K29 case_pointer_head_score (CASE_FEAT_POINTER_SCORE): the head of a teacher-forced scoring pass.  For row r with target y = targets[r]:
  *   gen_y = exp(logits[r, y] - max) / sum_i exp(logits[r, i] - max);   pm = softmax(mix_logits[r, 0 .. nmem]);
  *   ptr   = sum_k pm[1 + k] sum_{positions s of memory k whose source id is y} copies[k][r, s];
@@ -658,6 +688,11 @@ int case_encoder_chain(const CaseEncoderChainDesc* d, const void* x_in, const vo
  * copy of (out, len) replaces the reference's `.item()` per generated token.  Pass -1 for a special id the vocabulary lacks. */
 int case_sentence_compact(const int64_t* ids, int64_t* out, int32_t* len, int64_t B, int64_t T, int64_t bos, int64_t pad,
                           int64_t eos, case_stream_t stream);
+
+/* K33 (CASE_FEAT_NGRAM_BAN): the reference's remove_duplicate (common/Utils.py:170-193) on case_sentence_compact's outputs, in place.  Per row,
+ * with L = len[b]: while L > n, cut at the largest i in [1, L - n] such that every token of out[b, i .. L) also occurs in out[b, 0 .. i); stop
+ * when there is none.  PAD is written behind the new length and len[b] updated.  One wave per row; T <= 256 (CASE_E_UNSUPPORTED beyond), n >= 1. */
+int case_remove_duplicate_ids(int64_t* out, int32_t* len, int64_t B, int64_t T, int32_t n, int64_t pad, case_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Consensus (minimum-Bayes-risk) selection over a pool of candidates, and ROUGE-L on token ids (CASE_FEAT_CONSENSUS; purely additive,
