@@ -545,9 +545,11 @@ __global__ void concat5_bwd_kernel(const T* __restrict__ d_out, const T* __restr
       const T* g = d_out + r * 5 * H + c;
       const float ev = Elem<T>::ld(e + i), x1 = Elem<T>::ld(a1 + i), x2 = Elem<T>::ld(a2 + i);
       const float g3 = Elem<T>::ld(g + 3 * H), g4 = Elem<T>::ld(g + 4 * H);
-      ge = Elem<T>::ld(g) + g3 * x1 + g4 * x2;
-      g1 = Elem<T>::ld(g + H) + g3 * ev;
-      g2 = Elem<T>::ld(g + 2 * H) + g4 * ev;
+      // explicit fmaf, in the order of the vector form below: left to the contraction pass the two forms (and the lanes of one vector)
+      // got different mixes of fused and separately rounded products, so the same element differed in its last f32 bit between them
+      ge = fmaf(g4, x2, fmaf(g3, x1, Elem<T>::ld(g)));
+      g1 = fmaf(g3, ev, Elem<T>::ld(g + H));
+      g2 = fmaf(g4, ev, Elem<T>::ld(g + 2 * H));
     }
     Elem<T>::st(de + i, ge);
     Elem<T>::st(da1 + i, g1);
@@ -606,9 +608,9 @@ __global__ void concat5_bwd_vec_kernel(const T* __restrict__ d_out, const T* __r
       Vec16<T>::load(g + 4 * H, g4);
 #pragma unroll
       for (int k = 0; k < E; ++k) {
-        ge[k] = ge[k] + g3[k] * x1[k] + g4[k] * x2[k];
-        g1[k] = g1[k] + g3[k] * ev[k];
-        g2[k] = g2[k] + g4[k] * ev[k];
+        ge[k] = fmaf(g4[k], x2[k], fmaf(g3[k], x1[k], ge[k]));  // (explicit: see concat5_bwd_kernel)
+        g1[k] = fmaf(g3[k], ev[k], g1[k]);
+        g2[k] = fmaf(g4[k], ev[k], g2[k]);
       }
     } else {
 #pragma unroll

@@ -1344,8 +1344,11 @@ class FanOutFn(Function):
             return gs[0], None
         dt = gs[0].dtype
         ev = 8 if dt == torch.bfloat16 else 4
+        # (a contiguous gradient may still start at an odd storage offset -- torch.cat's backward hands out such slices -- and case_add_n
+        #  takes 16-byte aligned sources only; a non-contiguous one is copied by add_n into a fresh, aligned allocation)
         if (not gs[0].is_cuda or dt not in (torch.bfloat16, torch.float32) or gs[0].numel() % ev or len(gs) > 8
-                or any(g.dtype != dt or g.shape != gs[0].shape for g in gs)):
+                or any(g.dtype != dt or g.shape != gs[0].shape for g in gs)
+                or any(g.is_contiguous() and g.data_ptr() % 16 for g in gs)):
             total = gs[0]
             for g in gs[1:]:
                 total = total + g
