@@ -171,6 +171,7 @@ class CaSE(nn.Module):
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
+        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30) or "bleu" (K34 + K35, BLEU-4 with add-one smoothing)
         # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
         # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
         self.no_repeat_ngram = 0
@@ -245,7 +246,7 @@ class CaSE(nn.Module):
         rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram))
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
-    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, **sampling):
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, metric=None, **sampling):
         """Consensus (minimum-Bayes-risk) selection under ROUGE-L (eval mode only): the answer is the candidate of a pool with the highest
         expected ROUGE-L F against the pool, instead of the pool's slot 0.  ``pool="sample"``: ``do_sample`` with ``self.sampling`` overridden
         by ``**sampling`` (``num_samples`` defaults to ``self.consensus_samples``); ``pool="beam"``: ``do_beam`` (``width=`` may be given), the
@@ -253,9 +254,11 @@ class CaSE(nn.Module):
         only the encode stages run for ``rank``.  ``valid`` bool [B, N] and ``weights`` f32 [B, N] (default uniform; e.g. the posterior
         exp(-length x ``sample_scores``)) as in ``evaluation.consensus``.  N <= 64, T <= 256, ids < 2^31; an empty candidate counts as [UNK].
         -> the pool's dict with ``answer`` [B, T] replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility`` [B, N] (-inf where
-        invalid) and ``pairwise_f`` [B, N, N].  Nothing is read back: with a sample pool at an integer ``seed`` the pass captures into one graph."""
+        invalid) and ``pairwise_f`` [B, N, N].  ``metric`` ("rouge_l" or "bleu"; None: ``self.consensus_metric``) chooses the utility; under
+        "bleu" (sentence BLEU-4 with add-one smoothing) the matrix is returned as ``pairwise_bleu``.  Nothing is read back: with a sample pool
+        at an integer ``seed`` the pass captures into one graph."""
         return consensus_answers(self, data, lambda d: self._encode_select_extract(d)[2][0], pool, candidates, valid, weights,
-                                 no_repeat_ngram=no_repeat_ngram, **sampling)
+                                 no_repeat_ngram=no_repeat_ngram, metric=metric, **sampling)
 
     def do_score(self, data, answers=None):
         """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at

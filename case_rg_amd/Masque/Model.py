@@ -120,6 +120,7 @@ class Masque(nn.Module):
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
+        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30) or "bleu" (K34 + K35, BLEU-4 with add-one smoothing)
         # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
         # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
         self.no_repeat_ngram = 0
@@ -189,12 +190,12 @@ class Masque(nn.Module):
         rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram))
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
-    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, **sampling):
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, metric=None, **sampling):
         """Consensus (minimum-Bayes-risk) selection under ROUGE-L over a sample pool, a beam pool or explicit ``candidates`` (eval mode only;
         see CaSE.do_consensus): the pool's dict with ``answer`` replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility``
-        [B, N] and ``pairwise_f`` [B, N, N]."""
+        [B, N] and ``pairwise_f`` [B, N, N] (``metric="bleu"``: ``pairwise_bleu``; None: ``self.consensus_metric``)."""
         return consensus_answers(self, data, lambda d: self._encode_select(d)[2][0], pool, candidates, valid, weights,
-                                 no_repeat_ngram=no_repeat_ngram, **sampling)
+                                 no_repeat_ngram=no_repeat_ngram, metric=metric, **sampling)
 
     def do_score(self, data, answers=None):
         """The probability of given answers under the model (eval mode only; see CaSE.do_score): ``answers`` int64 [B, T'] or [B, N, T'],

@@ -296,3 +296,31 @@ class CumulativeTrainer(object):
         if items == 0:
             return dict(rouge_l=float('nan'), items=0)
         return dict(rouge_l=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
+
+    def evaluate_bleu(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False):
+        """BLEU of ``model(data, method)['answer']`` against ``data[references]`` (as ``evaluate_rouge`` takes them), without building a Python
+        string: ``evaluation.eval_bleu_ids`` per batch (K34 + K35: nltk's ``sentence_bleu`` with default arguments, all present ground truths
+        of an item as its references), the sum kept on the device, one read-back at the end -> dict(bleu = the mean of the per-item BLEU x 100
+        rounded to 2 decimals -- ``evaluation.eval_bleu``'s number for ``predict`` + ``to_sentence``, what the reference's ``eval_bleu_file``
+        prints for the same tokens --, items = the items counted).  ``remove_duplicates`` as in ``evaluate_rouge``.  One process, under no_grad
+        in eval mode; the model's mode is restored afterwards."""
+        from ..evaluation.ngram_ids import eval_bleu_ids
+        from ..evaluation.rouge_ids import model_specials
+        was_training = self.model.training
+        self.model.eval()
+        specials = model_specials(self.model.vocab2id)
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    out = self.model(data, method=method)
+                    part = eval_bleu_ids(out['answer'], data[references], specials, remove_duplicates=remove_duplicates).sum()
+                    total = part if total is None else total + part
+                    items += out['answer'].shape[0]
+        finally:
+            self.model.train(was_training)
+        if items == 0:
+            return dict(bleu=float('nan'), items=0)
+        return dict(bleu=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)

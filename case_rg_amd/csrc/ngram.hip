@@ -1,0 +1,273 @@
+// BLEU and n-gram overlap on token ids (evaluation/bleu.py restated on ids; the reference's Eval_Bleu.py / Eval_Overlap.py).
+//   K34 case_ngram_counts  per (hypothesis, reference) and per order k = 1..4: the clipped k-gram matches, the number of distinct hypothesis
+//                          k-grams that occur in the reference, and both against all present references at once; exact integers
+//   K35 case_bleu_scores   the counts -> sentence BLEU of every pair and against all present references (f64, fixed order)
+// Nothing here waits for the host, and the library keeps no state.
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <stdint.h>
+
+#include "case_hip.h"
+#include "common.h"
+
+constexpr int NGRAM_MAX_TA = 256;  // 4 words of 64 hypothesis positions
+constexpr int NGRAM_WAVES = 4;     // hypotheses per workgroup
+constexpr int NGRAM_ORDERS = 4;
+
+// ---- K34 -------------------------------------------------------------------------------------------------------------------------
+// One wave per hypothesis (b, n), held as K30 holds it: lane l has a[l + 64 j] for word j, the sentinel -1 from a_len on.  For a token t at
+// position p of some sequence s,  M(p) = __ballot(tok == t)  marks the hypothesis positions that hold t, and
+//     D_1(p) = M(p),   D_k(p) = M(p) & (D_{k-1}(p - 1) << 1)        (the shift carries bit 63 of word j into bit 0 of word j + 1)
+// has bit i set exactly when the k-gram of the hypothesis that ENDS at i equals the k-gram of s that ends at p.  The D_k are wave-uniform and
+// live from one token to the next (and from one 64-token load of s to the next); lane i adds its own bit of D_k(p) to a counter, which
+// after the last token is the number of times the k-gram ending at i occurs in s.  A bit below k - 1 or from a_len on is never set.
+//   s = the hypothesis itself gives c_hyp; a set bit with p < i says "this k-gram occurred earlier", and every lane but the one at the first
+//   occurrence then drops its count to 0, so a distinct k-gram is counted once.
+//   s = reference m gives c_ref:  clip = sum over the lanes of min(c_hyp, c_ref),  hit = the number of lanes with both > 0;  the per-lane
+//   maximum of c_ref over the present references gives clip_any / hit_any after the last one.
+struct NgramMasks {
+  unsigned long long d[NGRAM_ORDERS - 1];  // D_1 .. D_3 of the previous position, one word
+};
+
+// The lane's own bit of a wave-uniform mask: the mask is used as a lane condition directly (one v_cndmask), no 64-bit shift per lane.
+__device__ __forceinline__ int ngram_own_bit(const unsigned long long d) { return __builtin_amdgcn_inverse_ballot_w64(d) ? 1 : 0; }
+
+// One token: the orders go downwards, so that D_k(p) is built from D_{k-1}(p - 1) before that is overwritten; use(k - 1, j, word j of D_k(p)).
+template <int WORDS, typename Use>
+__device__ __forceinline__ void ngram_step(const int32_t (&tok)[WORDS], const int t, NgramMasks (&prev)[WORDS], Use use) {
+  unsigned long long match[WORDS];
+#pragma unroll
+  for (int j = 0; j < WORDS; ++j) match[j] = __ballot(tok[j] == t);
+#pragma unroll
+  for (int k = NGRAM_ORDERS - 1; k > 0; --k)
+#pragma unroll
+    for (int j = 0; j < WORDS; ++j) {
+      const unsigned long long below = j > 0 ? prev[j - 1].d[k - 1] >> 63 : 0ull;
+      const unsigned long long d = match[j] & ((prev[j].d[k - 1] << 1) | below);
+      use(k, j, d);
+      if (k + 1 < NGRAM_ORDERS) prev[j].d[k] = d;
+    }
+#pragma unroll
+  for (int j = 0; j < WORDS; ++j) {
+    use(0, j, match[j]);
+    prev[j].d[0] = match[j];
+  }
+}
+
+__device__ __forceinline__ int ngram_wave_sum(int v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// sum over the wave of min(c_hyp, c) per order (each at most 256: two orders share one 32-bit sum) and the count of lanes with both > 0
+template <int WORDS>
+__device__ __forceinline__ void ngram_totals(const int (&c_hyp)[NGRAM_ORDERS][WORDS], const int (&c)[NGRAM_ORDERS][WORDS], int (&clip)[NGRAM_ORDERS],
+                                             int (&hit)[NGRAM_ORDERS]) {
+  int part[NGRAM_ORDERS];
+#pragma unroll
+  for (int k = 0; k < NGRAM_ORDERS; ++k) {
+    part[k] = 0;
+    hit[k] = 0;
+#pragma unroll
+    for (int j = 0; j < WORDS; ++j) {
+      part[k] += c_hyp[k][j] < c[k][j] ? c_hyp[k][j] : c[k][j];
+      hit[k] += __popcll(__ballot(c_hyp[k][j] > 0 && c[k][j] > 0));
+    }
+  }
+  const int lo = ngram_wave_sum(part[0] | (part[1] << 16)), hi = ngram_wave_sum(part[2] | (part[3] << 16));
+  clip[0] = lo & 0xffff;
+  clip[1] = lo >> 16;
+  clip[2] = hi & 0xffff;
+  clip[3] = hi >> 16;
+}
+
+__device__ __forceinline__ void ngram_store(int32_t* __restrict__ out, const int (&v)[NGRAM_ORDERS]) {
+#pragma unroll
+  for (int k = 0; k < NGRAM_ORDERS; ++k) out[k] = v[k];
+}
+
+template <int WORDS>
+__global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_counts_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
+                                                                       const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
+                                                                       int32_t* __restrict__ clip, int32_t* __restrict__ clip_any,
+                                                                       int32_t* __restrict__ hit, int32_t* __restrict__ hit_any,
+                                                                       int32_t* __restrict__ distinct, const int64_t BN, const int N, const int M,
+                                                                       const int Ta, const int Tb, const int max_n) {
+  const int lane = threadIdx.x & 63;
+  const int64_t h = (int64_t)blockIdx.x * NGRAM_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: the masks and the loops stay scalar)
+  if (h >= BN) return;  // (whole waves: no barrier follows)
+  const int64_t item = h / N;
+  int la = a_len[h];
+  la = la < 0 ? 0 : la > Ta ? Ta : la;
+  int32_t tok[WORDS];
+#pragma unroll
+  for (int j = 0; j < WORDS; ++j) {
+    const int pos = lane + 64 * j;
+    tok[j] = pos < la ? (int32_t)a[h * Ta + pos] : -1;
+  }
+  NgramMasks prev[WORDS];
+  int c_hyp[NGRAM_ORDERS][WORDS], c_ref[NGRAM_ORDERS][WORDS], c_max[NGRAM_ORDERS][WORDS], earlier[NGRAM_ORDERS][WORDS];
+#pragma unroll
+  for (int j = 0; j < WORDS; ++j) {
+#pragma unroll
+    for (int k = 0; k + 1 < NGRAM_ORDERS; ++k) prev[j].d[k] = 0ull;
+#pragma unroll
+    for (int k = 0; k < NGRAM_ORDERS; ++k) c_hyp[k][j] = c_max[k][j] = earlier[k][j] = 0;
+  }
+  // the hypothesis against itself
+#pragma unroll
+  for (int w = 0; w < WORDS; ++w) {
+    const int n = la - 64 * w < 64 ? la - 64 * w : 64;
+    for (int i = 0; i < n; ++i) {
+      const int t = __builtin_amdgcn_readlane(tok[w], i);
+      const int p = 64 * w + i;
+      ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) {
+        const int bit = ngram_own_bit(d);
+        c_hyp[k][j] += bit;
+        earlier[k][j] |= p < lane + 64 * j ? bit : 0;
+      });
+    }
+  }
+  int total[NGRAM_ORDERS];
+#pragma unroll
+  for (int k = 0; k < NGRAM_ORDERS; ++k) {
+    total[k] = 0;
+#pragma unroll
+    for (int j = 0; j < WORDS; ++j) {
+      if (earlier[k][j] || k >= max_n) c_hyp[k][j] = 0;
+      total[k] += __popcll(__ballot(c_hyp[k][j] > 0));
+    }
+  }
+  if (lane == 0) ngram_store(distinct + h * NGRAM_ORDERS, total);
+
+  int got_clip[NGRAM_ORDERS], got_hit[NGRAM_ORDERS];
+  for (int m = 0; m < M; ++m) {
+    const int64_t r = item * M + m;
+    int lb = b_len[r];
+    lb = lb < 0 ? 0 : lb > Tb ? Tb : lb;
+    const int64_t* __restrict__ row = b + r * Tb;
+#pragma unroll
+    for (int j = 0; j < WORDS; ++j) {
+#pragma unroll
+      for (int k = 0; k + 1 < NGRAM_ORDERS; ++k) prev[j].d[k] = 0ull;
+#pragma unroll
+      for (int k = 0; k < NGRAM_ORDERS; ++k) c_ref[k][j] = 0;
+    }
+    if (la > 0) {
+      for (int t0 = 0; t0 < lb; t0 += 64) {  // (prev carries D_k(p - 1) from one load to the next)
+        const int mine = t0 + lane < lb ? (int32_t)row[t0 + lane] : -1;
+        const int n = lb - t0 < 64 ? lb - t0 : 64;
+        for (int i = 0; i < n; ++i) {
+          const int t = __builtin_amdgcn_readlane(mine, i);
+          ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { c_ref[k][j] += ngram_own_bit(d); });
+        }
+      }
+    }
+    ngram_totals<WORDS>(c_hyp, c_ref, got_clip, got_hit);
+#pragma unroll
+    for (int k = 0; k < NGRAM_ORDERS; ++k)
+#pragma unroll
+      for (int j = 0; j < WORDS; ++j) c_max[k][j] = c_ref[k][j] > c_max[k][j] ? c_ref[k][j] : c_max[k][j];
+    if (lane == 0) {
+      ngram_store(clip + (h * M + m) * NGRAM_ORDERS, got_clip);
+      ngram_store(hit + (h * M + m) * NGRAM_ORDERS, got_hit);
+    }
+  }
+  ngram_totals<WORDS>(c_hyp, c_max, got_clip, got_hit);
+  if (lane == 0) {
+    ngram_store(clip_any + h * NGRAM_ORDERS, got_clip);
+    ngram_store(hit_any + h * NGRAM_ORDERS, got_hit);
+  }
+}
+
+// ---- K35 -------------------------------------------------------------------------------------------------------------------------
+// nltk's sentence_bleu with uniform weights over the orders 1..max_n (evaluation/bleu.py sentence_bleu, in its order): p_k = clip_k / max(1, la - k + 1),
+// add1: (clip_k + 1) / (max(1, la - k + 1) + 1) for k >= 2;  score = BP exp(sum_k ln p_k / max_n),  BP = 1 if la > r else exp(1 - r / la);
+// 0 when a precision it takes the logarithm of is 0 (none: any order; add1: the first), and without a present reference.
+__device__ __forceinline__ double bleu_of(const int32_t* __restrict__ clip, const int la, const int r, const int max_n, const int smoothing, double* bp_out) {
+#pragma clang fp contract(off)
+  double bp = 0.0;
+  if (la > 0 && r > 0) bp = la > r ? 1.0 : exp(1.0 - (double)r / (double)la);
+  if (bp_out) *bp_out = bp;
+  if (la <= 0 || r <= 0) return 0.0;
+  double s = 0.0;
+  for (int k = 0; k < max_n; ++k) {
+    int num = clip[k], den = la - k > 1 ? la - k : 1;
+    if (smoothing == 1 && k > 0) {
+      num += 1;
+      den += 1;
+    }
+    if (num <= 0) return 0.0;
+    s += log((double)num / (double)den);
+  }
+  return bp * exp(s / (double)max_n);
+}
+
+// One thread per (hypothesis (b, n), m): m < M is the pair score against reference m; m == M is the score against all present references
+// (r = the present length closest to la, the shorter one on a tie).
+__global__ __launch_bounds__(256) void bleu_scores_kernel(const int32_t* __restrict__ clip, const int32_t* __restrict__ clip_any,
+                                                          const int32_t* __restrict__ a_len, const int32_t* __restrict__ b_len,
+                                                          float* __restrict__ bleu_pair, double* __restrict__ bleu_any, double* __restrict__ bp,
+                                                          const int64_t total, const int N, const int M, const int max_n, const int smoothing) {
+  const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (at >= total) return;
+  const int64_t h = at / (M + 1);
+  const int m = (int)(at - h * (M + 1));
+  const int64_t item = h / N;
+  const int la = a_len[h] < 0 ? 0 : a_len[h];  // (no Ta here: the caller keeps the lengths within K34's 0 .. Ta / Tb, see case_hip.h)
+  if (m < M) {
+    bleu_pair[h * M + m] = (float)bleu_of(clip + (h * M + m) * NGRAM_ORDERS, la, b_len[item * M + m], max_n, smoothing, nullptr);
+    return;
+  }
+  int best = 0, gap = 0;
+  for (int i = 0; i < M; ++i) {
+    const int lb = b_len[item * M + i];
+    if (lb <= 0) continue;
+    const int d = lb > la ? lb - la : la - lb;
+    if (best == 0 || d < gap || (d == gap && lb < best)) {
+      best = lb;
+      gap = d;
+    }
+  }
+  double item_bp;
+  bleu_any[h] = bleu_of(clip_any + h * NGRAM_ORDERS, la, best, max_n, smoothing, &item_bp);
+  if (bp) bp[h] = item_bp;
+}
+
+// ---- C ABI -----------------------------------------------------------------------------------------------------------------------
+extern "C" int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* clip, int32_t* clip_any,
+                                 int32_t* hit, int32_t* hit_any, int32_t* distinct, int64_t B, int64_t N, int64_t M, int64_t Ta, int64_t Tb,
+                                 int32_t max_n, case_stream_t stream) {
+  CASE_REQUIRE(a && a_len && b && b_len && clip && clip_any && hit && hit_any && distinct && B > 0 && N > 0 && M > 0 && Ta > 0 && Tb > 0 &&
+                   B < (1ll << 31) && N < (1ll << 24) && M < (1ll << 24) && B * N < (1ll << 31) && Tb < (1ll << 30) && max_n >= 1 &&
+                   max_n <= NGRAM_ORDERS,
+               "case_ngram_counts: bad argument");
+  if (Ta > NGRAM_MAX_TA)
+    return case_set_error(CASE_E_UNSUPPORTED, "case_ngram_counts: hypotheses of up to %d positions (got %lld)", NGRAM_MAX_TA, (long long)Ta);
+  const int64_t BN = B * N;
+  const dim3 grid((unsigned)((BN + NGRAM_WAVES - 1) / NGRAM_WAVES)), block(64 * NGRAM_WAVES);
+  if (Ta <= 64)
+    hipLaunchKernelGGL(ngram_counts_kernel<1>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
+                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
+  else if (Ta <= 128)
+    hipLaunchKernelGGL(ngram_counts_kernel<2>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
+                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
+  else
+    hipLaunchKernelGGL(ngram_counts_kernel<4>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
+                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
+  return case_check_launch("case_ngram_counts");
+}
+
+extern "C" int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t* a_len, const int32_t* b_len, float* bleu_pair,
+                                double* bleu_any, double* bp, int64_t B, int64_t N, int64_t M, int32_t max_n, int32_t smoothing,
+                                case_stream_t stream) {
+  CASE_REQUIRE(clip && clip_any && a_len && b_len && bleu_pair && bleu_any && B > 0 && N > 0 && M > 0 && B < (1ll << 31) && N < (1ll << 24) &&
+                   M < (1ll << 24) && B * N < (1ll << 31) && B * N * (M + 1) < (1ll << 39) && max_n >= 1 && max_n <= NGRAM_ORDERS &&
+                   (smoothing == 0 || smoothing == 1),
+               "case_bleu_scores: bad argument");
+  const int64_t total = B * N * (M + 1);
+  hipLaunchKernelGGL(bleu_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, clip, clip_any, a_len, b_len,
+                     bleu_pair, bleu_any, bp, total, (int)N, (int)M, (int)max_n, (int)smoothing);
+  return case_check_launch("case_bleu_scores");
+}

@@ -63,23 +63,33 @@ def eval_rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
     return torch.where(out["ref_valid"], f, torch.zeros_like(f)).max(dim=1)[0] * 100
 
 
-def consensus(candidates, specials, valid=None, weights=None):
+CONSENSUS_METRICS = ("rouge_l", "bleu")
+
+
+def consensus(candidates, specials, valid=None, weights=None, metric="rouge_l"):
     """candidates int64 [B, N, T] (raw ids: ``do_sample``'s ``samples``, ``do_beam``'s ``beam_answers``), specials = (bos, pad, eos, unk),
     valid bool [B, N] (default: all), weights f32 [B, N] (default: uniform; e.g. a posterior exp(-len x sample_scores)) ->
     dict(answer int64 [B, T] = the raw row of the pick, consensus_index int64 [B], consensus_utility f32 [B, N], pairwise_f f32 [B, N, N]).
     The pick of item b maximises  sum_m w[b, m] F(candidate n as the hypothesis, m as the reference) / sum_m w[b, m]  over the valid
-    candidates, the self term included, the lowest index on ties; an invalid candidate reads -inf and is never picked."""
+    candidates, the self term included, the lowest index on ties; an invalid candidate reads -inf and is never picked.
+    ``metric="bleu"``: the utility F is sentence BLEU-4 with add-one smoothing (K34 + K35 on the pool against itself; unsmoothed sentence BLEU
+    is 0 for most short pairs and useless as a utility), and the dict carries ``pairwise_bleu`` f32 [B, N, N] instead of ``pairwise_f``."""
     bos, pad, eos, unk = specials
+    if metric not in CONSENSUS_METRICS:
+        raise ValueError("consensus: metric must be one of %s, not %r" % (CONSENSUS_METRICS, metric))
     if not torch.is_tensor(candidates) or candidates.dtype != torch.int64 or candidates.dim() != 3:
         raise TypeError("consensus: candidates must be an int64 tensor [B, N, T]")
     N, T = candidates.shape[1:]
     if not ops.consensus_supported(N, T):
         raise ValueError("consensus: pools of up to %d candidates of up to %d positions (got %d x %d)" % (ops.CONSENSUS_MAX_N, ops.LCS_MAX_T, N, T))
     kept, count = _compact(candidates, bos, pad, eos, unk)
-    _, f = ops.lcs_pairs(kept, count, kept, count)
+    if metric == "bleu":
+        f = ops.bleu_scores(ops.ngram_counts(kept, count, kept, count, 4), count, count, 4, "add1")[0]
+    else:
+        _, f = ops.lcs_pairs(kept, count, kept, count)
     weights = None if weights is None else weights.to(device=candidates.device, dtype=torch.float32)
     utility, index, answer = ops.consensus_pick(f, weights, valid, candidates)
-    return dict(answer=answer, consensus_index=index, consensus_utility=utility, pairwise_f=f)
+    return {"answer": answer, "consensus_index": index, "consensus_utility": utility, "pairwise_" + ("bleu" if metric == "bleu" else "f"): f}
 
 
 def model_specials(vocab2id):
@@ -88,12 +98,17 @@ def model_specials(vocab2id):
     return tuple(vocab2id[w] for w in (BOS_WORD, PAD_WORD, EOS_WORD, UNK_WORD))
 
 
-def consensus_answers(model, data, rank_of, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, **sampling):
+def consensus_answers(model, data, rank_of, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, metric=None,
+                      **sampling):
     """``do_consensus`` of the task models (CaSE, Masque): build the pool with the model's own decoders (or take ``candidates``), then
     ``consensus``.  ``rank_of(data)``: the model's passage ranking from its encode stages alone.  ``no_repeat_ngram`` goes to the pool's decoder
-    (None: the model's attribute); explicit candidates are taken as they are."""
+    (None: the model's attribute); explicit candidates are taken as they are.  ``metric``: "rouge_l" or "bleu" (None: the model's
+    ``consensus_metric``), checked before anything is decoded."""
     if model.training:
         raise ValueError("do_consensus runs in eval mode: call model.eval() first")
+    metric = model.consensus_metric if metric is None else metric
+    if metric not in CONSENSUS_METRICS:
+        raise ValueError("do_consensus: metric must be one of %s, not %r" % (CONSENSUS_METRICS, metric))
     if candidates is None and pool in ("sample", "beam"):
         sampling["no_repeat_ngram"] = no_repeat_ngram
     if candidates is not None:
@@ -112,5 +127,5 @@ def consensus_answers(model, data, rank_of, pool="sample", candidates=None, vali
         valid = finite if valid is None else finite & valid.to(finite.device).bool()
     else:
         raise ValueError("do_consensus: pool must be 'sample' or 'beam' (or give candidates), not %r" % (pool,))
-    out.update(consensus(pool_ids, model_specials(model.vocab2id), valid=valid, weights=weights))
+    out.update(consensus(pool_ids, model_specials(model.vocab2id), valid=valid, weights=weights, metric=metric))
     return out

@@ -2367,3 +2367,66 @@ def consensus_pick(f, weights, valid, candidates):
     A.call("case_consensus_pick", _ptr(f), _ptr(weights), _ptr(_u8(valid)), _ptr(candidates), _ptr(utility), _ptr(index), _ptr(answer), B, N, T,
            _stream())
     return utility, index, answer
+
+
+# K34 / K35: n-gram counts and BLEU on token ids
+NGRAM_MAX_T, NGRAM_MAX_ORDER = 256, 4
+BLEU_SMOOTHINGS = {"none": 0, "add1": 1}
+
+
+def ngram_supported(Ta, max_n=4):
+    """Hypotheses of Ta positions and orders 1 .. max_n: K34 holds a hypothesis in 4 x 64 match-mask bits and counts four orders."""
+    return 1 <= Ta <= NGRAM_MAX_T and 1 <= max_n <= NGRAM_MAX_ORDER and bool(A.lib.case_abi_features() & A.FEAT_NGRAM_COUNTS)
+
+
+def _ngram_pairs(what, a_len, b_len, max_n):
+    """The checks K34 and K35 share: the hypothesis lengths int32 [B, N], the reference lengths int32 [B, M], the order range."""
+    if not isinstance(max_n, int) or not 1 <= max_n <= NGRAM_MAX_ORDER:
+        raise ValueError("%s: max_n in 1..%d (got %r)" % (what, NGRAM_MAX_ORDER, max_n))
+    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or a_len.dim() != 2 or b_len.dim() != 2 or a_len.shape[0] != b_len.shape[0]:
+        raise TypeError("%s: the lengths must be int32 [B, N] and [B, M]" % what)
+
+
+def ngram_counts(a, a_len, b, b_len, max_n=4):
+    """K34: a int64 [B, N, Ta] / a_len int32 [B, N] (front-packed hypotheses and their lengths, as ``sentence_compact`` writes them), b int64
+    [B, M, Tb] / b_len int32 [B, M] (references; ``b_len`` 0: absent) -> dict of exact int32 counts, the order k = 1..4 on the last axis (0
+    above ``max_n``): clip [B, N, M, 4] (clipped k-gram matches against reference m), clip_any [B, N, 4] (against the per-k-gram maximum over
+    the present references: multi-reference BLEU's numerator), hit [B, N, M, 4] / hit_any [B, N, 4] (distinct hypothesis k-grams that occur
+    in reference m / in any present one), distinct [B, N, 4].  Ta <= 256; ids must lie in [0, 2^31) (not checked: compared on 32 bits)."""
+    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
+        raise TypeError("ngram_counts: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
+    B, N, Ta = a.shape
+    M, Tb = b.shape[1], b.shape[2]
+    _ngram_pairs("ngram_counts", a_len, b_len, max_n)
+    if tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
+        raise TypeError("ngram_counts: the lengths must be int32 [B, N] and [B, M]")
+    if Ta > NGRAM_MAX_T:
+        raise ValueError("ngram_counts: hypotheses of up to %d positions (got %d)" % (NGRAM_MAX_T, Ta))
+    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
+    new = lambda *shape: torch.empty(*shape, NGRAM_MAX_ORDER, dtype=torch.int32, device=a.device)  # noqa: E731
+    out = dict(clip=new(B, N, M), clip_any=new(B, N), hit=new(B, N, M), hit_any=new(B, N), distinct=new(B, N))
+    A.call("case_ngram_counts", _ptr(a), _ptr(a_len), _ptr(b), _ptr(b_len), _ptr(out["clip"]), _ptr(out["clip_any"]), _ptr(out["hit"]),
+           _ptr(out["hit_any"]), _ptr(out["distinct"]), B, N, M, Ta, Tb, max_n, _stream())
+    return out
+
+
+def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
+    """K35: ``counts`` (``ngram_counts``' dict: ``clip`` and ``clip_any`` are read) and the lengths it was given -> (bleu_pair f32 [B, N, M]:
+    sentence BLEU of hypothesis n against the single reference m, f64 rounded once; bleu f64 [B, N]: against all present references;
+    bp f64 [B, N]: the brevity penalty of ``bleu``).  evaluation.bleu.sentence_bleu's definition; ``smoothing`` "none" or "add1"."""
+    if smoothing not in BLEU_SMOOTHINGS:
+        raise ValueError("bleu_scores: smoothing must be 'none' or 'add1', not %r" % (smoothing,))
+    _ngram_pairs("bleu_scores", a_len, b_len, max_n)
+    B, N = a_len.shape
+    M = b_len.shape[1]
+    clip, clip_any = counts["clip"], counts["clip_any"]
+    if clip.dtype != torch.int32 or clip_any.dtype != torch.int32 or tuple(clip.shape) != (B, N, M, NGRAM_MAX_ORDER) or \
+            tuple(clip_any.shape) != (B, N, NGRAM_MAX_ORDER):
+        raise TypeError("bleu_scores: counts['clip'] / ['clip_any'] must be int32 [B, N, M, 4] / [B, N, 4] for lengths [B, N] and [B, M]")
+    clip, clip_any, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (clip, clip_any, a_len, b_len))
+    pair = torch.empty(B, N, M, dtype=torch.float32, device=clip.device)
+    bleu = torch.empty(B, N, dtype=torch.float64, device=clip.device)
+    bp = torch.empty(B, N, dtype=torch.float64, device=clip.device)
+    A.call("case_bleu_scores", _ptr(clip), _ptr(clip_any), _ptr(a_len), _ptr(b_len), _ptr(pair), _ptr(bleu), _ptr(bp), B, N, M, max_n,
+           BLEU_SMOOTHINGS[smoothing], _stream())
+    return pair, bleu, bp

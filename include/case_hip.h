@@ -75,7 +75,8 @@ enum {
   CASE_FEAT_SAMPLE_DECODE = 1u << 19,     /* K28 case_pointer_head_sample */
   CASE_FEAT_POINTER_SCORE = 1u << 20,     /* K29 case_pointer_head_score */
   CASE_FEAT_CONSENSUS = 1u << 21,         /* K30 / K31 case_lcs_pairs / case_consensus_pick */
-  CASE_FEAT_NGRAM_BAN = 1u << 22          /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
+  CASE_FEAT_NGRAM_BAN = 1u << 22,         /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
+  CASE_FEAT_NGRAM_COUNTS = 1u << 23       /* K34 / K35 case_ngram_counts / case_bleu_scores */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -716,6 +717,34 @@ int case_lcs_pairs(const int64_t* a, const int32_t* a_len, const int64_t* b, con
                    int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream);
 int case_consensus_pick(const float* f, const float* w, const uint8_t* valid, const int64_t* cand, float* utility, int64_t* index,
                         int64_t* answer, int64_t B, int64_t N, int64_t T, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * BLEU and n-gram overlap on token ids (CASE_FEAT_NGRAM_COUNTS; purely additive, generation 600 unchanged).  The metrics are nltk's
+ * sentence_bleu, which evaluation/Eval_Bleu.py calls with default arguments, and evaluation/Eval_Overlap.py's distinct-set overlap.
+ * K34 case_ngram_counts: a, a_len, b, b_len exactly as case_lcs_pairs takes them (front-packed ids, lengths clamped to 0 .. Ta / Tb, ids
+ *   compared on their low 32 bits, Ta <= 256 or CASE_E_UNSUPPORTED, Tb without such a limit); max_n in 1 .. 4.  With count_s(g) the number of
+ *   times the k-gram g occurs in sequence s, for every order k = 1 .. max_n (index k - 1 of the last axis; the orders above max_n read 0):
+ *     clip[b, n, m, k]   = sum over the distinct k-grams g of hypothesis n of min(count_hyp(g), count_ref_m(g))
+ *     clip_any[b, n, k]  = the same sum with max over the present references m (b_len > 0) of count_ref_m(g) in place of count_ref_m(g)
+ *     hit[b, n, m, k]    = the number of distinct hypothesis k-grams that occur in reference m;  hit_any[b, n, k]: in any present reference
+ *     distinct[b, n, k]  = the number of distinct hypothesis k-grams
+ *   all int32 and exact; an absent reference (b_len == 0) reads 0.  The k-gram total of a hypothesis is max(a_len - k + 1, 0).
+ * K35 case_bleu_scores: with la = a_len[b, n], p_k = clip_k / max(1, la - k + 1) (smoothing 1, "add one": (clip_k + 1) / (max(1, la - k + 1) + 1)
+ *   for k >= 2) and r a reference length
+ *     score = BP exp(sum_{k = 1 .. max_n} ln p_k / max_n),   BP = 1 if la > r, else exp(1 - r / la)
+ *   in f64, k ascending, without contraction; exactly 0 when a p_k is 0 and when la == 0 or there is no reference.
+ *     bleu_pair[b, n, m] (f32, rounded once) from clip[b, n, m, :] with r = b_len[b, m];
+ *     bleu_any[b, n] (f64) from clip_any[b, n, :] with r = the present b_len[b, m] closest to la, the shorter one on a tie;
+ *     bp[b, n] (f64, may be NULL) = the BP of bleu_any (0 without a present reference).
+ *   smoothing: 0 none, 1 add one (Lin & Och 2004; nltk's SmoothingFunction.method2).
+ *   K35 has no Ta / Tb and takes the lengths as they are (a negative one as 0), where K34 clamps them to 0 .. Ta / Tb: pass lengths within
+ *   those ranges (case_sentence_compact's always are), or the two kernels see different lengths for the same row.
+ * ------------------------------------------------------------------------------------------- */
+int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* clip, int32_t* clip_any,
+                      int32_t* hit, int32_t* hit_any, int32_t* distinct, int64_t B, int64_t N, int64_t M, int64_t Ta, int64_t Tb,
+                      int32_t max_n, case_stream_t stream);
+int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t* a_len, const int32_t* b_len, float* bleu_pair,
+                     double* bleu_any, double* bp, int64_t B, int64_t N, int64_t M, int32_t max_n, int32_t smoothing, case_stream_t stream);
 
 #ifdef __cplusplus
 }
