@@ -182,12 +182,15 @@ class CaSE(nn.Module):
     def to_sentence(self, data, batch_indices):
         return to_sentence(batch_indices, self.id2vocab)
 
-    def _encode_select_extract(self, data):
+    def _encode_select(self, data):
         if self.query_encoder is self.passage_encoder:  # one shared encoder (reference :262-263): both inputs in one pass
             eq, ep = self.query_encoder.forward_many([data['query'], data['passage']])
         else:
             eq, ep = self.query_encoder(data['query']), self.passage_encoder(data['passage'])
-        ps = self.passage_selection.action(data['query'], data['passage'], encode_query=eq, encode_passage=ep)
+        return eq, ep, self.passage_selection.action(data['query'], data['passage'], encode_query=eq, encode_passage=ep)
+
+    def _encode_select_extract(self, data):
+        eq, ep, ps = self._encode_select(data)
         se = self.span_extraction.action(data['query'], data['passage'], encode_query=eq, encode_passage=ep,
                                          passage_selection_result=ps)
         return eq, ep, ps, se
@@ -276,6 +279,14 @@ class CaSE(nn.Module):
         out['rank'] = rank
         return out
 
+    def do_rank(self, data):
+        """The passage ranking alone (eval mode only): the encoders and the selection stage run, the token-identification stage and the
+        decoder do not -> {'rank': [B, P]}, the bits of ``do_test(data)['rank']``.  ``evaluation.rank_metrics_ids`` and
+        ``CumulativeTrainer.evaluate_rank`` score it."""
+        if self.training:
+            raise ValueError("do_rank runs in eval mode: call model.eval() first")
+        return {'rank': self._encode_select(data)[2][0]}
+
     def forward(self, data, method='mle_train'):
         # the reference expands data['source_map'] into a dense one-hot here (Utils.build_map, 15 GB at cfg 2);
         # the ids themselves feed the pointer scatter kernel instead
@@ -291,3 +302,5 @@ class CaSE(nn.Module):
             return self.do_score(data)
         elif method == 'consensus':
             return self.do_consensus(data)
+        elif method == 'rank':
+            return self.do_rank(data)

@@ -207,6 +207,13 @@ class Masque(nn.Module):
         out['rank'] = rank
         return out
 
+    def do_rank(self, data):
+        """The passage ranking alone (eval mode only; see CaSE.do_rank): the encoders and the selection stage run, the decoder does not
+        -> {'rank': [B, P]}, the bits of ``do_test(data)['rank']``."""
+        if self.training:
+            raise ValueError("do_rank runs in eval mode: call model.eval() first")
+        return {'rank': self._encode_select(data)[2][0]}
+
     def forward(self, data, method='mle_train'):
         if method == 'train':
             return self.do_train(data)
@@ -222,3 +229,5 @@ class Masque(nn.Module):
             return self.do_score(data)
         elif method == 'consensus':
             return self.do_consensus(data)
+        elif method == 'rank':
+            return self.do_rank(data)

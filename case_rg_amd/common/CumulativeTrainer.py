@@ -324,3 +324,32 @@ class CumulativeTrainer(object):
         if items == 0:
             return dict(bleu=float('nan'), items=0)
         return dict(bleu=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
+
+    def evaluate_rank(self, dataset, collate_fn, batch_size, method='rank', labels='passage_label', keys=None, valid=None):
+        """The TREC ranking metrics of ``model(data, method)['rank']`` [B, P] against ``data[labels]`` (int64 [B]: the index of the gold
+        passage; or an integer [B, P] tensor of grades), every item its own query: ``evaluation.eval_rank_ids`` per batch (K36), the column
+        sums kept on the device, one read-back at the end -> dict(map, ndcg, recall_5 .. recall_1000, recip_rank, P_1 = the plain means over
+        the items, unrounded f64 -- what the reference's ``eval_trec_file`` prints for the run ``save_result`` writes, plus recip_rank and
+        P_1 --, items = the items counted).  ``method="rank"`` stops after the selection stage; any method whose result carries ``rank`` may
+        be named.  ``keys`` / ``valid`` name optional ``data`` entries (tie keys, the larger first; which slots hold a passage).  One
+        process, under no_grad in eval mode; the model's mode is restored afterwards."""
+        from .. import ops
+        from ..evaluation.rank_ids import eval_rank_ids
+        was_training = self.model.training
+        self.model.eval()
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    rank = self.model(data, method=method)['rank']
+                    part = eval_rank_ids(rank, data[labels], None if keys is None else data[keys], None if valid is None else data[valid])
+                    total = part if total is None else total + part
+                    items += rank.shape[0]
+        finally:
+            self.model.train(was_training)
+        if items == 0:
+            return dict({name: float('nan') for name in ops.RANK_METRICS}, items=0)
+        sums = total.tolist()  # (the one read-back of the evaluation)
+        return dict({name: s / items for name, s in zip(ops.RANK_METRICS, sums)}, items=items)

@@ -2430,3 +2430,43 @@ def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
     A.call("case_bleu_scores", _ptr(clip), _ptr(clip_any), _ptr(a_len), _ptr(b_len), _ptr(pair), _ptr(bleu), _ptr(bp), B, N, M, max_n,
            BLEU_SMOOTHINGS[smoothing], _stream())
     return pair, bleu, bp
+
+
+# K36: TREC ranking metrics of score rows
+RANK_MAX_P, RANK_MAX_JUDGED = 1024, 2048
+RANK_CUTOFFS = (5, 10, 15, 20, 30, 100, 200, 500, 1000)
+RANK_METRICS = ("map", "ndcg") + tuple("recall_%d" % k for k in RANK_CUTOFFS) + ("recip_rank", "P_1")  # the columns of ``metrics``
+
+
+def rank_metrics(scores, rel, keys=None, valid=None, extra_rel=None):
+    """K36: scores f32 [B, P] (one query per row), rel int32 [B, P] (grades; relevant from 1 on, negative = 0), keys int32 [B, P] or None
+    (the column index; the LARGER key comes first among equal scores), valid bool [B, P] or None (all; an invalid slot is not retrieved and
+    its ``rel`` is ignored), extra_rel int32 [B, R] or None (grades of judged documents that were not retrieved; <= 0 = padding) ->
+    dict(order int32 [B, P]: the columns in rank order, -1 behind the retrieved ones; metrics f64 [B, 13] in the order of ``RANK_METRICS``;
+    num_rel int32 [B]).  evaluation.trec's definitions.  P <= 1024, P + R <= 2048."""
+    if scores.dtype != torch.float32 or scores.dim() != 2:
+        raise TypeError("rank_metrics: scores must be f32 [B, P]")
+    B, P = scores.shape
+    if rel.dtype != torch.int32 or tuple(rel.shape) != (B, P):
+        raise TypeError("rank_metrics: rel must be int32 [B, P]")
+    if keys is not None and (keys.dtype != torch.int32 or tuple(keys.shape) != (B, P)):
+        raise TypeError("rank_metrics: keys must be int32 [B, P]")
+    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, P)):
+        raise TypeError("rank_metrics: valid must be bool [B, P]")
+    if extra_rel is not None and (extra_rel.dtype != torch.int32 or extra_rel.dim() != 2 or extra_rel.shape[0] != B):
+        raise TypeError("rank_metrics: extra_rel must be int32 [B, R]")
+    R = 0 if extra_rel is None else extra_rel.shape[1]
+    if B < 1 or P < 1:
+        raise ValueError("rank_metrics: at least one query and one document slot (got [%d, %d])" % (B, P))
+    if P > RANK_MAX_P or P + R > RANK_MAX_JUDGED:
+        raise ValueError("rank_metrics: up to %d retrieved and %d judged documents per query (got %d and %d)" % (
+            RANK_MAX_P, RANK_MAX_JUDGED, P, P + R))
+    scores, rel = (t if t.is_contiguous() else t.contiguous() for t in (scores, rel))
+    keys = None if keys is None else keys.contiguous()
+    extra_rel = None if R == 0 else extra_rel.contiguous()
+    order = torch.empty(B, P, dtype=torch.int32, device=scores.device)
+    metrics = torch.empty(B, len(RANK_METRICS), dtype=torch.float64, device=scores.device)
+    num_rel = torch.empty(B, dtype=torch.int32, device=scores.device)
+    A.call("case_rank_metrics", _ptr(scores), _ptr(keys), _ptr(rel), _ptr(_u8(valid)), _ptr(extra_rel), _ptr(order), _ptr(metrics),
+           _ptr(num_rel), B, P, R, _stream())
+    return dict(order=order, metrics=metrics, num_rel=num_rel)

@@ -76,7 +76,8 @@ enum {
   CASE_FEAT_POINTER_SCORE = 1u << 20,     /* K29 case_pointer_head_score */
   CASE_FEAT_CONSENSUS = 1u << 21,         /* K30 / K31 case_lcs_pairs / case_consensus_pick */
   CASE_FEAT_NGRAM_BAN = 1u << 22,         /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
-  CASE_FEAT_NGRAM_COUNTS = 1u << 23       /* K34 / K35 case_ngram_counts / case_bleu_scores */
+  CASE_FEAT_NGRAM_COUNTS = 1u << 23,      /* K34 / K35 case_ngram_counts / case_bleu_scores */
+  CASE_FEAT_RANK_METRICS = 1u << 24       /* K36 case_rank_metrics */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -745,6 +746,25 @@ int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, 
                       int32_t max_n, case_stream_t stream);
 int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t* a_len, const int32_t* b_len, float* bleu_pair,
                      double* bleu_any, double* bp, int64_t B, int64_t N, int64_t M, int32_t max_n, int32_t smoothing, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * TREC ranking metrics of score rows (CASE_FEAT_RANK_METRICS; purely additive, generation 600 unchanged): what evaluation/Eval_Trec.py
+ * asks pytrec_eval for (map, ndcg, recall), plus recip_rank and P_1; evaluation/trec.py states the definitions.
+ * K36 case_rank_metrics: every row b of scores f32 [B, P] is one query with P document slots; keys int32 [B, P] (NULL: the column index)
+ *   breaks ties, rel int32 [B, P] holds the grades, valid u8 [B, P] (NULL: all) says which slots were retrieved (the rel of any other is
+ *   ignored), extra_rel int32 [B, R] (NULL with R = 0) the grades of judged documents that were not retrieved (<= 0: padding).
+ *   Rank order: score descending, the larger key first among equal scores, the lower column among equal (score, key); -0.0 == +0.0, a NaN
+ *   score compares as -inf.  A document is relevant when its grade is >= 1, a negative grade counts as 0; num_rel counts the relevant ones
+ *   among the retrieved slots and extra_rel.
+ *     order[b, r]   int32: the column at rank r (0-based), -1 behind the retrieved ones
+ *     metrics[b, :] f64 x 13: map, ndcg (gain = grade, discount log2(rank + 1), ideal list over all judged grades), recall_5, _10, _15, _20,
+ *                   _30, _100, _200, _500, _1000 (relevant in the top min(k, retrieved) / num_rel), recip_rank, P_1; all 0 where num_rel == 0
+ *     num_rel[b]    int32
+ *   Counts are exact, every ratio is one f64 division, the f64 sums of map and ndcg go through a tree of fixed shape: two launches give the
+ *   same bits.  P <= 1024 and P + R <= 2048, or CASE_E_UNSUPPORTED.  Asynchronous on `stream`; every output element is written.
+ * ------------------------------------------------------------------------------------------- */
+int case_rank_metrics(const float* scores, const int32_t* keys, const int32_t* rel, const uint8_t* valid, const int32_t* extra_rel,
+                      int32_t* order, double* metrics, int32_t* num_rel, int64_t B, int64_t P, int64_t R, case_stream_t stream);
 
 #ifdef __cplusplus
 }
