@@ -18,7 +18,7 @@ WS_ATTENTION_SPLITKV, WS_ATTENTION_BWD, WS_OPTIM_SUMSQ, WS_ENCODER_CHAIN_PACK, W
 (FEAT_GEMM_256, FEAT_GEMM_SMALL, FEAT_ENCODER_CHAIN, FEAT_ATTN_SCORES, FEAT_ATTN_DECODE, FEAT_OPTIM, FEAT_ATTN_RESIDENT, FEAT_RESERVED_CUS,
  FEAT_GEMM_DW_SLABS, FEAT_DECODER_CHAIN, FEAT_ATTN_DECODE_MQA, FEAT_POINTER_DECODE, FEAT_POINTER_HEAD, FEAT_GEMM_LN, FEAT_STEP_STATE,
  FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS, FEAT_NGRAM_BAN,
- FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS) = (1 << i for i in range(25))
+ FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS, FEAT_POINTER_HEAD_WIDE) = (1 << i for i in range(26))
 EPI_BIAS_COL, EPI_BIAS_ROW, EPI_GELU, EPI_RELU = 1, 2, 4, 8
 EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ATOMIC, EPI_DROPOUT = 16, 32, 64, 128, 256
 
@@ -126,6 +126,10 @@ SIGNATURES = {
     "case_pointer_head_decode": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr],
     "case_pointer_head_beam": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, i32, ptr],
     "case_pointer_head_sample": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32, ptr],
+    "case_pointer_head_decode_wide": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr, i64, ptr, i64, i64, i32, i64, ptr],
+    "case_pointer_head_beam_wide": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, i32, ptr, i64, ptr, i64, i64, i32, i64, ptr],
+    "case_pointer_head_sample_wide": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32,
+                                      ptr, i64, ptr, i64, i64, i32, ptr],
     "case_pointer_head_score": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64, ptr, ptr, i64, i64, i64, ptr],
     "case_beam_advance": [ptr] * 12 + [i64, i64, i64, i32, i64, ptr],
     "case_pointer_head_decode_ban": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr, i64, i64, i32, i64, ptr],

@@ -549,8 +549,8 @@ class PointerDecoderCore(nn.Module):
             mode, n = _BeamMode(self, B, W, T, dev, ngram), W
         elif sampling:
             if not ops.sample_supported(self.tgt_vocab_size):
-                raise RuntimeError("sampled decoding: the vocabulary (%d) is beyond what the sampling kernel holds in LDS (V <= 36000)"
-                                   % self.tgt_vocab_size)
+                raise RuntimeError("sampled decoding: this build of the library cannot draw from a vocabulary of %d (CASE_FEAT_SAMPLE_DECODE, "
+                                   "CASE_FEAT_POINTER_HEAD_WIDE)" % self.tgt_vocab_size)
             mode, n = _SampleMode(B, T, dev, sampling, ngram), int(sampling["num_samples"])
         else:
             mode, n = _GreedyMode(self, B, T, dev, ngram), 1

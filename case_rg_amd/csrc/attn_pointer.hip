@@ -476,6 +476,8 @@ struct HeadArgs {
   float* top;               // [B] or null: dist[id]
   int64_t V, S;
   int nmem;
+  float* row_ws;            // the wide forms: [B, row_stride] f32 rows in device memory (null: the LDS forms)
+  int64_t row_stride;
 };
 
 // ---- K32: the n-gram ban behind the row build ------------------------------------------------------------------------------------------
@@ -515,6 +517,9 @@ __device__ __forceinline__ void ngram_ban_row(float* row, const int64_t V, const
 
 // the row build shared by K23 and its beam form: row[0 .. V) = pm_0 softmax(logits) + the pointer mass of the sorted source keys (gen written
 // on the way when asked for).  Ends behind a barrier: every thread may read the whole row.
+// WIDE (the row in device memory): the exponentials are formed from the logits again where the LDS form reads them back from the row -- the
+// same instructions on the same operands, so the same bits, with one write of the row where the LDS form makes three.
+template <bool WIDE = false>
 __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float* row, uint32_t* tk, float* tv, float* red, const int64_t b) {
   const int64_t V = a.V;
   const int tid = threadIdx.x;
@@ -538,20 +543,20 @@ __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float*
   float mx = -INFINITY;
   for (int64_t i = tid; i < V; i += PH_THREADS) {
     const float x = lg[i];
-    row[i] = x;
+    if constexpr (!WIDE) row[i] = x;
     mx = fmaxf(mx, x);
   }
   mx = block_max(mx, red);
   float sum = 0.f;
   for (int64_t i = tid; i < V; i += PH_THREADS) {
-    const float e = __expf(row[i] - mx);
-    row[i] = e;
+    const float e = __expf((WIDE ? lg[i] : row[i]) - mx);
+    if constexpr (!WIDE) row[i] = e;
     sum += e;
   }
   sum = block_sum(sum, red);
   const float inv = 1.f / sum;
   for (int64_t i = tid; i < V; i += PH_THREADS) {
-    const float g = row[i] * inv;
+    const float g = (WIDE ? __expf(lg[i] - mx) : row[i]) * inv;
     if (a.gen) a.gen[b * V + i] = g;
     row[i] = pm[0] * g;
   }
@@ -594,18 +599,20 @@ __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float*
   }
 }
 
-template <bool BAN>
+// WIDE: the row lives in a.row_ws (device memory) and LDS holds the staging and scratch only.  A workgroup reads back its own global stores
+// behind __syncthreads() (one CU, one L1); no row is shared between workgroups.
+template <bool BAN, bool WIDE = false>
 __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
-  float* row = ph_smem;                                  // [V]
-  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
+  float* row = WIDE ? a.row_ws + (int64_t)blockIdx.x * a.row_stride : ph_smem;  // [V]
+  uint32_t* tk = reinterpret_cast<uint32_t*>(WIDE ? ph_smem : ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
   float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);                       // [PH_THREADS]
   float* red = tv + PH_THREADS;                                                    // [64] reduction scratch
   __shared__ int64_t best_i[16];
   __shared__ float best_v[16];
   const int64_t b = blockIdx.x, V = a.V;
   const int tid = threadIdx.x;
-  pointer_head_build_row(a, row, tk, tv, red, b);
+  pointer_head_build_row<WIDE>(a, row, tk, tv, red, b);
   if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));
   // outputs: the distribution row and its argmax (lowest index on ties)
   float bv = -INFINITY;
@@ -650,12 +657,12 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
 // W largest entries with the lowest id first on ties, whatever the scheduling; round 0 is K23's argmax comparison for comparison, so W = 1
 // returns K23's id and value bit for bit.  Scratch on top of K23's: two words for the previous winner.
 constexpr int PH_MAX_W = 8;
-template <bool BAN>
+template <bool BAN, bool WIDE = false>
 __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const HeadArgs a, float* __restrict__ cand_p, int64_t* __restrict__ cand_id,
                                                                        const int W, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
-  float* row = ph_smem;
-  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
+  float* row = WIDE ? a.row_ws + (int64_t)blockIdx.x * a.row_stride : ph_smem;
+  uint32_t* tk = reinterpret_cast<uint32_t*>(WIDE ? ph_smem : ph_smem + ((a.V + 3) & ~(int64_t)3));
   float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);
   float* red = tv + PH_THREADS;
   __shared__ int64_t best_i[16];
@@ -664,7 +671,7 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const Hea
   __shared__ float win_v;
   const int64_t b = blockIdx.x, V = a.V;
   const int tid = threadIdx.x;
-  pointer_head_build_row(a, row, tk, tv, red, b);
+  pointer_head_build_row<WIDE>(a, row, tk, tv, red, b);
   if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));  // (K25 appends: a slot's history is its hypothesis)
   float pv = INFINITY;  // the previous round's winner: round 0 admits every entry
   int64_t pi = -1;
@@ -920,11 +927,14 @@ __device__ __forceinline__ float sample_scan64(float x, int lane) {  // inclusiv
   return x;
 }
 
-template <bool BAN>
+// WIDE: the row in a.row_ws, or -- a ready distribution with no workspace given (the host's choice: 16-byte aligned rows, no ban) -- `dist_in`
+// itself, which no pass writes.  The quads read up to three floats behind V inside the row's stride; those entries are never kept.
+template <bool BAN, bool WIDE = false>
 __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s, const BanArgs nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
-  float* row = ph_smem;
-  uint32_t* tk = reinterpret_cast<uint32_t*>(ph_smem + ((a.V + 3) & ~(int64_t)3));
+  const bool in_place = WIDE && !a.row_ws;  // (block-uniform)
+  float* row = !WIDE ? ph_smem : in_place ? const_cast<float*>(s.dist_in) + (int64_t)blockIdx.x * a.V : a.row_ws + (int64_t)blockIdx.x * a.row_stride;
+  uint32_t* tk = reinterpret_cast<uint32_t*>(WIDE ? ph_smem : ph_smem + ((a.V + 3) & ~(int64_t)3));
   float* tv = reinterpret_cast<float*>(tk + PH_THREADS + 4);
   float* red = tv + PH_THREADS;
   unsigned long long* hist = reinterpret_cast<unsigned long long*>(tk);  // [256]: the key staging is dead behind the row build
@@ -936,8 +946,8 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
   const int64_t b = blockIdx.x;
   const int V = (int)a.V, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   if (a.logits) {
-    pointer_head_build_row(a, row, tk, tv, red, b);
-  } else {
+    pointer_head_build_row<WIDE>(a, row, tk, tv, red, b);
+  } else if (!in_place) {
     for (int i = tid; i < V; i += PH_THREADS) row[i] = s.dist_in[b * a.V + i];
     __syncthreads();
   }
@@ -1463,20 +1473,37 @@ static int pointer_head_fill(Args& a, const char* who, const float* logits, cons
 }
 
 constexpr int64_t PH_MAX_V = 36000, PS_MAX_V = 131071;  // the vocabulary row in LDS; the key format alone
+// K28's wide `dist_in` form: a histogram bin sums at most V fixed-point masses, each below 2^40 (the largest q lies below 2^e and the scale is
+// 2^(40 - e)), so V <= 2^24 keeps every 64-bit sum below 2^64; the entry counts and the int ids need less
+constexpr int64_t PW_MAX_DIST_V = 1ll << 24;
 
 static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
-                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S) {
-  const int rc = pointer_head_fill(a, who, logits, mix_logits, keys, copies, lens, nmem, B, V, S, PH_MAX_V,
-                                   " (run the softmax / scatter / argmax launches)");
+                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S,
+                             bool wide = false) {
+  const int rc = pointer_head_fill(a, who, logits, mix_logits, keys, copies, lens, nmem, B, V, S, wide ? PS_MAX_V : PH_MAX_V,
+                                   wide ? "" : " (run the softmax / scatter / argmax launches)");
   if (rc != CASE_OK) return rc;
   a.gen = gen;
   a.dist = dist;
   a.ids = nullptr;
   a.top = nullptr;
+  a.row_ws = nullptr;
+  a.row_stride = 0;
   return CASE_OK;
 }
 
+// the LDS forms: the row, the key staging and the reduction scratch; the wide forms (V = 0): the staging and the scratch alone
 static size_t pointer_head_lds(int64_t V) { return (size_t)(((V + 3) & ~(int64_t)3) + (PH_THREADS + 4) + PH_THREADS + 64) * 4; }
+
+// the row workspace of the wide forms: [R, row_stride] f32, row_stride >= V and a multiple of 4, 16-byte aligned (K28 reads float4)
+static int pointer_head_workspace(HeadArgs& a, const char* who, float* row_ws, int64_t row_stride, int64_t V) {
+  CASE_REQUIRE(row_ws && row_stride >= V && row_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(row_ws) & 15) == 0,
+               "%s: the row workspace must be 16-byte aligned f32 [rows, row_stride], row_stride >= V and a multiple of 4", who);
+  a.row_ws = row_ws;
+  a.row_stride = row_stride;
+  return CASE_OK;
+}
+
 
 // the dynamic-LDS ceiling of a kernel that keeps the vocabulary row in LDS, raised once per process (``done``: the caller's static flag)
 static int pointer_head_reserve(const void* kernel, bool& done, const char* who) {
@@ -1496,6 +1523,30 @@ static int pointer_head_ban(BanArgs& nb, const char* who, const int32_t* hist, i
   nb.t = (int)t;
   nb.n = (int)n;
   return CASE_OK;
+}
+
+// the wide forms take the history operands always: hist == NULL or n == 0 means no ban
+static int pointer_head_ban_opt(BanArgs& nb, bool& ban, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos) {
+  ban = hist != nullptr && n != 0;
+  nb = BanArgs();
+  return ban ? pointer_head_ban(nb, who, hist, Tmax, t, n, eos) : CASE_OK;
+}
+
+template <bool BAN>
+static int pointer_head_decode_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
+                                           const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids,
+                                           float* top, int64_t B, int64_t V, int64_t S, float* row_ws, int64_t row_stride, const BanArgs& nb,
+                                           case_stream_t stream) {
+  CASE_REQUIRE(ids, "%s: bad argument", who);
+  HeadArgs a;
+  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S, true);
+  if (rc != CASE_OK) return rc;
+  rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
+  if (rc != CASE_OK) return rc;
+  a.ids = ids;
+  a.top = top;
+  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, true>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, nb);
+  return case_check_launch(who);
 }
 
 template <bool BAN>
@@ -1533,6 +1584,53 @@ extern "C" int case_pointer_head_decode_ban(const float* logits, const float* mi
                                           nb, stream);
 }
 
+extern "C" int case_pointer_head_decode_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                             const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                             int64_t V, int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t,
+                                             int32_t n, int64_t eos, case_stream_t stream) {
+  const char* who = "case_pointer_head_decode_wide";
+  BanArgs nb;
+  bool ban;
+  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return ban ? pointer_head_decode_wide_launch<true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws, row_stride,
+                                                     nb, stream)
+             : pointer_head_decode_wide_launch<false>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws,
+                                                      row_stride, nb, stream);
+}
+
+template <bool BAN>
+static int pointer_head_beam_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
+                                         const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p,
+                                         int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride,
+                                         const BanArgs& nb, case_stream_t stream) {
+  CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
+  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
+  HeadArgs a;
+  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S, true);
+  if (rc != CASE_OK) return rc;
+  rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
+  if (rc != CASE_OK) return rc;
+  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, true>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, cand_p,
+                     cand_id, (int)W, nb);
+  return case_check_launch(who);
+}
+
+extern "C" int case_pointer_head_beam_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                           const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                           int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
+                                           int64_t t, int32_t n, int64_t eos, case_stream_t stream) {
+  const char* who = "case_pointer_head_beam_wide";
+  BanArgs nb;
+  bool ban;
+  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return ban ? pointer_head_beam_wide_launch<true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
+                                                   row_stride, nb, stream)
+             : pointer_head_beam_wide_launch<false>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
+                                                    row_stride, nb, stream);
+}
+
 template <bool BAN>
 static int pointer_head_beam_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                     const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V,
@@ -1568,24 +1666,34 @@ extern "C" int case_pointer_head_beam_ban(const float* logits, const float* mix_
                                         W, nb, stream);
 }
 
-template <bool BAN>
+template <bool BAN, bool WIDE = false>
 static int pointer_head_sample_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                       const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
                                       uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
                                       float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad,
-                                      int32_t first, int32_t last, const BanArgs& nb, case_stream_t stream) {
+                                      int32_t first, int32_t last, const BanArgs& nb, case_stream_t stream, float* row_ws = nullptr,
+                                      int64_t row_stride = 0) {
   CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "%s: bad argument", who);
   CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f, "%s: temperature must be > 0, top_k >= 0 and top_p in (0, 1]", who);
   CASE_REQUIRE((logits != nullptr) != (dist_in != nullptr), "%s: give either the logits or a ready distribution", who);
   HeadArgs a;
   if (logits) {
-    const int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
+    const int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S, WIDE);
     if (rc != CASE_OK) return rc;
   } else {
-    if (V > PH_MAX_V) return case_set_error(CASE_E_UNSUPPORTED, "%s: built for V <= %lld", who, (long long)PH_MAX_V);
+    const int64_t max_v = WIDE ? PW_MAX_DIST_V : PH_MAX_V;
+    if (V > max_v) return case_set_error(CASE_E_UNSUPPORTED, "%s: built for V <= %lld", who, (long long)max_v);
     a = HeadArgs();
     a.dist = dist;
     a.V = V;
+  }
+  if constexpr (WIDE) {
+    // a ready distribution is read where it lies when its rows are 16-byte aligned and nothing is to be zeroed in them
+    const bool in_place = !logits && !BAN && V % 4 == 0 && (reinterpret_cast<uintptr_t>(dist_in) & 15) == 0;
+    if (!in_place) {
+      const int rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
+      if (rc != CASE_OK) return rc;
+    }
   }
   SampleArgs s;
   s.dist_in = dist_in;
@@ -1604,6 +1712,10 @@ static int pointer_head_sample_launch(const char* who, const float* logits, cons
   s.top_k = top_k;
   s.first = first;
   s.last = last;
+  if constexpr (WIDE) {
+    hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, true>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, s, nb);
+    return case_check_launch(who);
+  }
   static bool attr = false;
   const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel<BAN>), attr, who);
   if (rc != CASE_OK) return rc;
@@ -1633,6 +1745,25 @@ extern "C" int case_pointer_head_sample_ban(const float* logits, const float* mi
   return pointer_head_sample_launch<true>("case_pointer_head_sample_ban", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob,
                                           ended, uniforms, R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb,
                                           stream);
+}
+
+extern "C" int case_pointer_head_sample_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                             const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                             float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
+                                             int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
+                                             int64_t unk, int64_t pad, int32_t first, int32_t last, float* row_ws, int64_t row_stride, int32_t* hist,
+                                             int64_t Tmax, int64_t t, int32_t n, case_stream_t stream) {
+  const char* who = "case_pointer_head_sample_wide";
+  BanArgs nb;
+  bool ban;
+  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
+  if (rc != CASE_OK) return rc;
+  return ban ? pointer_head_sample_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
+                                                      R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
+                                                      row_ws, row_stride)
+             : pointer_head_sample_launch<false, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
+                                                       R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
+                                                       row_ws, row_stride);
 }
 
 // K32 as a launch of its own (the unfused head): one wave per row zeroes the banned entries of dist [R, V] in place

@@ -1900,14 +1900,49 @@ def pointer_attend_decode(wq, eu, v, value, col_valid=None, row_valid=None, prio
 
 
 # K23: the greedy step's head (vocabulary softmax, mixing softmax, p0 x gen + pointer scatter, argmax) as one launch with the vocabulary
-# row in LDS.  "auto": a device-sorted source map, V <= 36000, <= 4 memories, inference; "off": the separate launches.
+# row in LDS (V <= 36000) or, in the wide form, in a device-memory workspace (V <= 131071).  "auto": a device-sorted source map, <= 4
+# memories, inference; "off": the separate launches.
 POINTER_HEAD = os.environ.get("CASE_POINTER_HEAD", "auto")
+HEAD_LDS_MAX_V = 36000  # K23 / K24 / K28 with the f32 vocabulary row in LDS
+HEAD_WIDE_MAX_V = 131071  # the wide forms with a built row: the SortedSource key format
+SAMPLE_WIDE_MAX_V = 1 << 24  # the wide K28 on a ready distribution: 2^24 fixed-point masses below 2^40 cannot overflow a 64-bit sum
+
+
+def pointer_head_wide_supported():
+    return bool(A.lib.case_abi_features() & A.FEAT_POINTER_HEAD_WIDE)
 
 
 def pointer_head_supported(source_map, V, nmem):
-    return (POINTER_HEAD != "off" and isinstance(source_map, SortedSource) and V <= 36000 and 1 <= nmem <= 4
+    return (POINTER_HEAD != "off" and isinstance(source_map, SortedSource) and 1 <= nmem <= 4
+            and (V <= HEAD_LDS_MAX_V or (V <= HEAD_WIDE_MAX_V and pointer_head_wide_supported()))
             and not torch.is_grad_enabled()  # (no autograd Function behind K23)
             and bool(A.lib.case_abi_features() & A.FEAT_POINTER_HEAD))
+
+
+def head_row_form(V, row="auto", who="pointer_head"):
+    """Where a head launch keeps its vocabulary row: "lds" (the LDS kernels, V <= 36000) or "global" (the wide kernels).  ``row`` = "auto"
+    is the LDS form wherever it fits and the wide form above; "lds" beyond 36000 is a ValueError."""
+    if row not in ("auto", "lds", "global"):
+        raise ValueError("%s: row must be 'auto', 'lds' or 'global' (got %r)" % (who, row))
+    if row == "lds" and V > HEAD_LDS_MAX_V:
+        raise ValueError("%s: row='lds' holds V <= %d in LDS (V %d)" % (who, HEAD_LDS_MAX_V, V))
+    if row == "auto":
+        row = "lds" if V <= HEAD_LDS_MAX_V else "global"
+    if row == "global" and not pointer_head_wide_supported():
+        raise RuntimeError("%s: this build of the library lacks the wide heads (CASE_FEAT_POINTER_HEAD_WIDE)" % who)
+    return row
+
+
+def _row_workspace(rows, V, dev):
+    """The wide heads' row workspace f32 [rows, row_stride]: -> (tensor, row_stride), row_stride the next multiple of 4 (the allocator's
+    blocks are 16-byte aligned and beyond)."""
+    stride = (V + 3) & ~3
+    return torch.empty(rows, stride, dtype=torch.float32, device=dev), stride
+
+
+def _ban_operands_wide(ban, rows, who):
+    """The history operands of a wide entry point: those of ``_ban_operands``, or (NULL, 0, 0, 0, -1) for no ban."""
+    return (None, 0, 0, 0, -1) if ban is None else _ban_operands(ban, rows, who)
 
 
 LINEAR_SKINNY = os.environ.get("CASE_LINEAR_SKINNY", "auto")  # "off": torch.cat + the GEMM path (A/B)
@@ -1958,17 +1993,22 @@ def _ban_operands(ban, rows, who):
     return _ptr(hist), hist.shape[1], int(t), int(n), -1 if eos is None else int(eos)
 
 
-def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None):
+def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None, row="auto"):
     """logits f32 [B, V]; mix_logits f32 [B, 1 + nmem]; source_map a SortedSource over the concatenated memories; copies: list of f32
     [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference).
-    ``ban`` = (hist int32 [B, Tmax], t, n, eos | None): K32, the n-gram ban before the argmax; the kernel appends ids at hist[:, t]."""
+    ``ban`` = (hist int32 [B, Tmax], t, n, eos | None): K32, the n-gram ban before the argmax; the kernel appends ids at hist[:, t].
+    ``row``: "auto" | "lds" | "global" (``head_row_form``); both forms return the same bits wherever both run."""
     B, V = logits.shape
+    row = head_row_form(V, row, "pointer_head_decode")
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_dist else None
     ids = torch.empty(B, dtype=torch.int64, device=logits.device)
     head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S)
-    if ban is None:
+    if row == "global":
+        ws, stride = _row_workspace(B, V, logits.device)
+        A.call("case_pointer_head_decode_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, B, "pointer_head_decode"), _stream())
+    elif ban is None:
         A.call("case_pointer_head_decode", *head, _stream())
     else:
         A.call("case_pointer_head_decode_ban", *head, *_ban_operands(ban, B, "pointer_head_decode"), _stream())
@@ -1979,18 +2019,23 @@ def beam_supported(width):
     return 1 <= width <= 8 and bool(A.lib.case_abi_features() & A.FEAT_BEAM_DECODE)
 
 
-def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False, ban=None):
+def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False, ban=None, row="auto"):
     """K24, ``pointer_head_decode`` with a top-``width`` tail: -> (gen [R, V] | None, dist [R, V] | None, cand_p f32 [R, W], cand_id int64 [R, W]),
     the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference).  ``ban`` as in
-    ``pointer_head_decode``, but the history is only read: row b * W + w is the hypothesis of slot w, which ``beam_advance`` maintains."""
+    ``pointer_head_decode``, but the history is only read: row b * W + w is the hypothesis of slot w, which ``beam_advance`` maintains.
+    ``row`` as in ``pointer_head_decode``."""
     R, V = logits.shape
+    row = head_row_form(V, row, "pointer_head_topk")
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
     gen = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_dist else None
     cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
     cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
     head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, S, width)
-    if ban is None:
+    if row == "global":
+        ws, stride = _row_workspace(R, V, logits.device)
+        A.call("case_pointer_head_beam_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, R, "pointer_head_topk"), _stream())
+    elif ban is None:
         A.call("case_pointer_head_beam", *head, _stream())
     else:
         A.call("case_pointer_head_beam_ban", *head, *_ban_operands(ban, R, "pointer_head_topk"), _stream())
@@ -1998,11 +2043,12 @@ def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=Fa
 
 
 def sample_supported(V):
-    return V <= 36000 and bool(A.lib.case_abi_features() & A.FEAT_SAMPLE_DECODE)
+    """K28 can draw from a distribution row of V entries: in LDS up to 36000, from device memory (the wide form) beyond."""
+    return (V <= HEAD_LDS_MAX_V or (V <= SAMPLE_WIDE_MAX_V and pointer_head_wide_supported())) and bool(A.lib.case_abi_features() & A.FEAT_SAMPLE_DECODE)
 
 
 def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, t_last, eos, unk, pad, temperature, top_k, top_p, rng=None,
-                        uniforms=None, dist_in=None, want_gen=False, want_dist=False, ban=None):
+                        uniforms=None, dist_in=None, want_gen=False, want_dist=False, ban=None, row="auto"):
     """K28, ``pointer_head_decode`` with a draw instead of the argmax: -> (gen [R, V] | None, dist [R, V] | None, ids int64 [R], prob f32 [R]).
     One token per row is drawn from the mixed distribution after temperature, top-k and top-p (the rule: include/case_hip.h); ``ids`` is what
     the reference's ``sample`` loop emits for it (UNK for EOS at the first step, EOS at the last, PAD behind the end) and ``ended`` (uint8 [R])
@@ -2011,6 +2057,7 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     at counter ``rng_base + offset + r``.  ``dist_in`` f32 [R, V] with ``logits=None`` draws from a ready distribution instead of building the row
     (``mix_logits`` / ``source_map`` / ``copies`` unused).  ``ban`` = (hist int32 [R, Tmax], t, n): K32, the n-gram ban before pmax, the cuts and
     the draw (either row source; no ban for a row that has ended or whose history holds ``eos``); the kernel appends ``ids`` at hist[:, t].
+    ``row`` as in ``pointer_head_decode``; the wide form reads an aligned ``dist_in`` where it lies (V a multiple of 4, no ban).
     No autograd (inference)."""
     if not (float(temperature) > 0.0) or int(top_k) < 0 or not (0.0 < float(top_p) <= 1.0):
         raise ValueError("pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]")
@@ -2023,6 +2070,7 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
         raise TypeError("pointer_head_sample: the row source must be f32 [R, V]")
     R, V = src.shape
     dev = src.device
+    row = head_row_form(V, row, "pointer_head_sample")
     src = src if src.is_contiguous() else src.contiguous()
     if ended.dtype != torch.uint8 or tuple(ended.shape) != (R,) or not ended.is_contiguous():
         raise TypeError("pointer_head_sample: ended must be a contiguous uint8 [R]")
@@ -2038,7 +2086,12 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     tail = (_ptr(gen), _ptr(dist), _ptr(ids), _ptr(prob), _ptr(ended), _ptr(uniforms), R, V)
     draw = (float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), int(seed), int(offset), state, int(eos), int(unk), int(pad),
             int(bool(t_first)), int(bool(t_last)))
-    if ban is None:
+    if row == "global":
+        in_place = logits is None and ban is None and V % 4 == 0 and src.data_ptr() % 16 == 0
+        ws, stride = (None, 0) if in_place else _row_workspace(R, V, dev)
+        hist = (None, 0, 0, 0) if ban is None else _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4]
+        entry, draw = "case_pointer_head_sample_wide", draw + (_ptr(ws), stride) + hist + (_stream(),)
+    elif ban is None:
         entry, draw = "case_pointer_head_sample", draw + (_stream(),)
     else:
         entry, draw = "case_pointer_head_sample_ban", draw + _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4] + (_stream(),)
@@ -2089,7 +2142,7 @@ def pointer_head_score(logits, mix_logits, source_map, rows_per_source, copies, 
 
 
 # K32: the n-gram ban.  The fused heads apply it behind their row build (``ban=`` above); ``ngram_ban_`` is the same rule as a launch of its own.
-NGRAM_MAX_T = 256  # a history is staged in LDS beside the vocabulary row
+NGRAM_MAX_T = 256  # a history is staged in LDS (beside the vocabulary row in the LDS heads)
 
 
 def ngram_ban_supported():

@@ -77,7 +77,8 @@ enum {
   CASE_FEAT_CONSENSUS = 1u << 21,         /* K30 / K31 case_lcs_pairs / case_consensus_pick */
   CASE_FEAT_NGRAM_BAN = 1u << 22,         /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
   CASE_FEAT_NGRAM_COUNTS = 1u << 23,      /* K34 / K35 case_ngram_counts / case_bleu_scores */
-  CASE_FEAT_RANK_METRICS = 1u << 24       /* K36 case_rank_metrics */
+  CASE_FEAT_RANK_METRICS = 1u << 24,      /* K36 case_rank_metrics */
+  CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25  /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -574,6 +575,31 @@ int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id, uint8_t* 
                           int64_t B, int32_t W, int64_t eos, const int32_t* flat_old, int32_t* flat_new, int64_t Tmax, case_stream_t stream);
 int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
                    case_stream_t stream);
+/* The wide forms of K23 / K24 / K28 (CASE_FEAT_POINTER_HEAD_WIDE; purely additive, generation 600 unchanged): the same kernels with the
+ * vocabulary row of a workgroup in device memory instead of LDS, for vocabularies beyond 36000 ids.  Each takes the arguments of its LDS
+ * sibling, then row_ws, row_stride, then the history operands of the `_ban` form (hist == NULL or n == 0: no ban; otherwise K32 exactly as above).
+ * row_ws f32 [rows, row_stride] is the caller's workspace: 16-byte aligned, row_stride >= V and a multiple of 4; its contents on entry do not
+ * matter and on return are unspecified.  One workgroup per row, as in the LDS forms; a workgroup touches its own row only.
+ * Every V from 1 up to the limit is accepted, and at any V the LDS form accepts the wide form returns the same bits in every output (the same
+ * per-thread strides, reduction order and tie rules), so everything stated for K23 / K24 / K28 / K32 holds here.
+ * Limits: a built row (logits != NULL) takes V <= 131071 (the key format of case_source_sort), nmem <= 4, S <= 32768; CASE_E_UNSUPPORTED beyond.
+ * case_pointer_head_sample_wide with logits == NULL draws from dist_in [R, V] for any V <= 16777216 = 2^24: the top-p cut sums fixed-point masses
+ * of 2^-40 of the largest entry's binade, each below 2^40, in 64-bit integers, and 2^24 of them cannot pass 2^64.  K28 leaves the row unchanged,
+ * so dist_in is read where it lies when it is 16-byte aligned, V is a multiple of 4 and no ban is asked (row_ws may then be NULL); otherwise
+ * it is copied into row_ws first.  dist_in itself is never written. */
+int case_pointer_head_decode_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                  const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                  int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                  case_stream_t stream);
+int case_pointer_head_beam_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                                int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W,
+                                float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                case_stream_t stream);
+int case_pointer_head_sample_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                                  int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob, uint8_t* ended,
+                                  const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k, float top_p, uint64_t seed,
+                                  uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
+                                  float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, case_stream_t stream);
 /* K29 case_pointer_head_score (CASE_FEAT_POINTER_SCORE): the head of a teacher-forced scoring pass.  For row r with target y = targets[r]:
  *   gen_y = exp(logits[r, y] - max) / sum_i exp(logits[r, i] - max);   pm = softmax(mix_logits[r, 0 .. nmem]);
  *   ptr   = sum_k pm[1 + k] sum_{positions s of memory k whose source id is y} copies[k][r, s];
