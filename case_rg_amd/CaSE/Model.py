@@ -11,7 +11,7 @@ import torch.nn as nn
 from .. import config, ops
 from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
-from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, no_repeat_ngram_param, sampling_params
+from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, decode_rules_param, no_repeat_ngram_param, sampling_params
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
 from ..evaluation.rouge_ids import consensus_answers
@@ -53,9 +53,10 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
-                score_index=None, no_repeat_ngram=0):
+                score_index=None, no_repeat_ngram=0, decode_rules=None):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram)
+                         score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram,
+                         decode_rules=decode_rules)
 
 
 class RelevantPassageSelection(nn.Module):
@@ -131,7 +132,8 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
-               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0):
+               span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0,
+               decode_rules=None):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -147,7 +149,7 @@ class ResponseGeneration(nn.Module):
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules)
 
 
 class CaSE(nn.Module):
@@ -175,6 +177,12 @@ class CaSE(nn.Module):
         # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
         # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
         self.no_repeat_ngram = 0
+        # Length and token rules of greedy, beam and sampled decoding (README "Length and token rules in decoding"); the keywords of do_test /
+        # do_beam / do_sample / do_consensus override them.  min_length: no EOS before that many tokens (0 = off); banned_ids: ids that are never
+        # emitted, [K] for every item or [B, K] per item (None = off); length_penalty: beam search ranks by cost / length^alpha (1.0 = the reference).
+        self.min_length = 0
+        self.banned_ids = None
+        self.length_penalty = 1.0
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -219,23 +227,35 @@ class CaSE(nn.Module):
         """The checked n-gram ban of a decoding call: the keyword, or the model's attribute when it is None."""
         return no_repeat_ngram_param(self.no_repeat_ngram if no_repeat_ngram is None else no_repeat_ngram, self.max_target_length)
 
-    def do_test(self, data, no_repeat_ngram=None):
+    def _rules(self, data, min_length=None, banned_ids=None, length_penalty=None):
+        """The checked decoding rules of a decoding call: the keywords, or the model's attributes where they are None."""
+        return decode_rules_param(self.min_length if min_length is None else min_length, self.banned_ids if banned_ids is None else banned_ids,
+                                  self.length_penalty if length_penalty is None else length_penalty, self.vocab2id, data['query'].size(0),
+                                  self.max_target_length, device=data['query'].device)
+
+    def do_test(self, data, no_repeat_ngram=None, min_length=None, banned_ids=None):
         """Greedy decoding.  ``no_repeat_ngram`` (None = ``self.no_repeat_ngram``; 0 = off): at every step the tokens that would complete an
-        n-gram the answer already holds get probability 0 before the argmax (K32); max_target_length <= 256 with it on."""
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, no_repeat_ngram=self._ngram(no_repeat_ngram))
+        n-gram the answer already holds get probability 0 before the argmax (K32); max_target_length <= 256 with it on.  ``min_length`` /
+        ``banned_ids`` (None = the model's attributes): no EOS among the first ``min_length`` tokens, and the listed ids ([K], or [B, K] per item)
+        are never emitted -- their entries of the distribution are zeroed before the argmax, nothing is renormalised."""
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, no_repeat_ngram=self._ngram(no_repeat_ngram),
+                                 decode_rules=self._rules(data, min_length, banned_ids))
         return {'answer': rg[3], 'rank': rank}
 
     do_infer = do_test  # BASELINE.json's wording
 
-    def do_beam(self, data, width=None, no_repeat_ngram=None):
+    def do_beam(self, data, width=None, no_repeat_ngram=None, min_length=None, banned_ids=None, length_penalty=None):
         """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``: ``width`` hypotheses per
         item ranked by length-normalised cost, retired on EOS): the ``do_test`` dict plus ``beam_score`` [B] (the answer's cum_cost / length),
-        ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer)."""
+        ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer).
+        ``min_length`` / ``banned_ids`` as in ``do_test``, for every slot of an item; ``length_penalty`` = alpha (None = the attribute; 1.0 = the
+        reference) ranks candidates and retired hypotheses by cum_cost / length^alpha, and ``beam_score`` / ``beam_scores`` are those keys."""
         rg, rank = self._respond(data, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width,
-                                 no_repeat_ngram=self._ngram(no_repeat_ngram))
+                                 no_repeat_ngram=self._ngram(no_repeat_ngram), decode_rules=self._rules(data, min_length, banned_ids, length_penalty))
         return {'answer': rg[3], 'rank': rank, 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
 
-    def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None, no_repeat_ngram=None):
+    def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None, no_repeat_ngram=None, min_length=None,
+                  banned_ids=None):
         """``do_test`` with every token DRAWN from the model's distribution (the reference's common/Generations.py ``sample`` loop; the draw is
         from the mixed pointer-generator distribution itself after ``temperature`` / ``top_k`` (0 = off) / ``top_p`` (1 = off), not from the
         reference's softmax of it): the ``do_test`` dict plus ``samples`` [B, N, T], ``sample_probs`` [B, N, T] (the model's unfiltered
@@ -244,12 +264,16 @@ class CaSE(nn.Module):
         every replay of a captured pass when a device step state is installed; without one a replay repeats its samples); an integer seed
         gives a private, reproducible pass and leaves the global stream untouched.  ``uniforms`` f32 [T, B * N] is the kernel's ``uniforms`` override
         handed up one layer, beyond the reference's interface: a caller with a stream of its own (antithetic or common random numbers across
-        models, a replayed draw) supplies u of row b N + n at step t as uniforms[t, b N + n]; it replaces ``seed`` and the counter generator."""
+        models, a replayed draw) supplies u of row b N + n at step t as uniforms[t, b N + n]; it replaces ``seed`` and the counter generator.
+        ``min_length`` / ``banned_ids`` as in ``do_test``, for every sample of an item, zeroed before the cuts and the draw; ``sample_probs``
+        stay the model's own probabilities.  With ``min_length`` >= 1 the UNK-for-EOS convention of the first step can no longer fire."""
         sampling = sampling_params(self.vocab2id, num_samples, temperature, top_k, top_p, seed, uniforms)
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram))
+        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram),
+                                 decode_rules=self._rules(data, min_length, banned_ids))
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
-    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, metric=None, **sampling):
+    def do_consensus(self, data, pool="sample", candidates=None, valid=None, weights=None, no_repeat_ngram=None, metric=None, min_length=None,
+                     banned_ids=None, length_penalty=None, **sampling):
         """Consensus (minimum-Bayes-risk) selection under ROUGE-L (eval mode only): the answer is the candidate of a pool with the highest
         expected ROUGE-L F against the pool, instead of the pool's slot 0.  ``pool="sample"``: ``do_sample`` with ``self.sampling`` overridden
         by ``**sampling`` (``num_samples`` defaults to ``self.consensus_samples``); ``pool="beam"``: ``do_beam`` (``width=`` may be given), the
@@ -259,9 +283,18 @@ class CaSE(nn.Module):
         -> the pool's dict with ``answer`` [B, T] replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility`` [B, N] (-inf where
         invalid) and ``pairwise_f`` [B, N, N].  ``metric`` ("rouge_l" or "bleu"; None: ``self.consensus_metric``) chooses the utility; under
         "bleu" (sentence BLEU-4 with add-one smoothing) the matrix is returned as ``pairwise_bleu``.  Nothing is read back: with a sample pool
-        at an integer ``seed`` the pass captures into one graph."""
+        at an integer ``seed`` the pass captures into one graph.  ``min_length`` / ``banned_ids`` (and ``length_penalty`` with ``pool="beam"``) go to
+        the pool's decoder as ``no_repeat_ngram`` does (None: the model's attributes); explicit candidates take none of them."""
         return consensus_answers(self, data, lambda d: self._encode_select_extract(d)[2][0], pool, candidates, valid, weights,
-                                 no_repeat_ngram=no_repeat_ngram, metric=metric, **sampling)
+                                 no_repeat_ngram=no_repeat_ngram, metric=metric, **self._pool_rules(pool, min_length, banned_ids, length_penalty), **sampling)
+
+    @staticmethod
+    def _pool_rules(pool, min_length, banned_ids, length_penalty):
+        """The rule keywords ``do_consensus`` hands to its pool's decoder (None stays out: the pool's decoder then takes the attributes)."""
+        if length_penalty is not None and pool != "beam":
+            raise ValueError("do_consensus: length_penalty belongs to pool='beam'")
+        given = dict(min_length=min_length, banned_ids=banned_ids, length_penalty=length_penalty)
+        return {k: v for k, v in given.items() if v is not None}
 
     def do_score(self, data, answers=None):
         """What the model thinks of answers that already exist (eval mode only): ``answers`` int64 [B, T'] or [B, N, T'] with PAD (0) at

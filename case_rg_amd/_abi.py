@@ -18,7 +18,7 @@ WS_ATTENTION_SPLITKV, WS_ATTENTION_BWD, WS_OPTIM_SUMSQ, WS_ENCODER_CHAIN_PACK, W
 (FEAT_GEMM_256, FEAT_GEMM_SMALL, FEAT_ENCODER_CHAIN, FEAT_ATTN_SCORES, FEAT_ATTN_DECODE, FEAT_OPTIM, FEAT_ATTN_RESIDENT, FEAT_RESERVED_CUS,
  FEAT_GEMM_DW_SLABS, FEAT_DECODER_CHAIN, FEAT_ATTN_DECODE_MQA, FEAT_POINTER_DECODE, FEAT_POINTER_HEAD, FEAT_GEMM_LN, FEAT_STEP_STATE,
  FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS, FEAT_NGRAM_BAN,
- FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS, FEAT_POINTER_HEAD_WIDE) = (1 << i for i in range(26))
+ FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS, FEAT_POINTER_HEAD_WIDE, FEAT_DECODE_RULES) = (1 << i for i in range(27))
 EPI_BIAS_COL, EPI_BIAS_ROW, EPI_GELU, EPI_RELU = 1, 2, 4, 8
 EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ATOMIC, EPI_DROPOUT = 16, 32, 64, 128, 256
 
@@ -59,6 +59,8 @@ class AttnProductDesc(C.Structure):
     _fields_ = [(n, i64) for n in ("N", "heads", "M", "Kc", "head_dim", "lda", "sa_seq", "sa_head", "ldb", "sb_seq", "sb_head",
                                    "ldc", "sc_seq", "sc_head")] + [("a_transposed", i32), ("alpha", f32)]
 
+
+_RULE = [i64, i32, ptr, i32, i64, i64]  # eos, min_length, banned, K, banned_stride, rows_per_item
 
 # name -> argument types (all return int); mirrors include/case_hip.h one to one
 SIGNATURES = {
@@ -139,6 +141,17 @@ SIGNATURES = {
     "case_beam_advance_ban": [ptr] * 12 + [i64, i64, i64, i32, i64, ptr, ptr, i64, ptr],
     "case_ngram_ban": [ptr, ptr, ptr, i64, i64, i64, i64, i32, i64, ptr],
     "case_remove_duplicate_ids": [ptr, ptr, i64, i64, i32, i64, ptr],
+    # the decoding rules: the `_ban` / `_wide` arguments, then eos, min_length, banned, K, item stride, rows_per_item
+    "case_pointer_head_decode_rules": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr, i64, i64, i32, i64] + _RULE + [ptr],
+    "case_pointer_head_beam_rules": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, i32, ptr, i64, i64, i32, i64] + _RULE + [ptr],
+    "case_pointer_head_sample_rules": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32,
+                                       ptr, i64, i64, i32] + _RULE + [ptr],
+    "case_pointer_head_decode_wide_rules": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, ptr, i64, ptr, i64, i64, i32, i64] + _RULE + [ptr],
+    "case_pointer_head_beam_wide_rules": [ptr] * 5 + [i32] + [ptr] * 4 + [i64, i64, i64, i32, ptr, i64, ptr, i64, i64, i32, i64] + _RULE + [ptr],
+    "case_pointer_head_sample_wide_rules": [ptr] * 5 + [i32] + [ptr] * 7 + [i64, i64, i64, f32, i32, f32, u64, u64, ptr, i64, i64, i64, i32, i32,
+                                            ptr, i64, ptr, i64, i64, i32] + _RULE + [ptr],
+    "case_row_rules": [ptr, ptr, i64, i64, i64] + _RULE + [ptr],
+    "case_beam_advance_rules": [ptr] * 12 + [i64, i64, i64, i32, i64, ptr, ptr, i64, f32, ptr],
     "case_beam_gather": [ptr, ptr, i32, ptr, ptr, ptr, i64, i32, i64, i64, i64, ptr],
     "case_beam_backtrack": [ptr] * 8 + [i64, i32, i64, ptr],
     "case_lcs_pairs": [ptr] * 6 + [i64, i64, i64, i64, i64, ptr],

@@ -125,6 +125,54 @@ def no_repeat_ngram_param(n, max_target_length=None):
     return n
 
 
+def decode_rules_param(min_length, banned_ids, length_penalty, vocab2id, B, max_target_length, device=None):
+    """The checked decoding rules of the decoders and the task models, in their device-ready form (made once per pass, not per step):
+    ``min_length`` an integer in [0, max_target_length - 1] (0 = off: EOS gets probability 0 at the steps t < min_length, and the last position can
+    always hold EOS); ``banned_ids`` None (off) or an integer tensor / sequence [K] (every item) or [B, K] (one list per item), K <=
+    ``ops.RULES_MAX_BANNED``, entries outside the vocabulary ignored (-1 pads a ragged list), duplicates legal, EOS refused (that is what
+    ``min_length`` is for); ``length_penalty`` a finite float >= 0 (1.0 = the reference's cost / length ranking of beam search).
+    -> dict(min_length, banned int32 tensor on ``device`` | None, length_penalty, eos); ``on`` says whether a row rule is set.
+    A pass that is captured into a graph takes ``banned_ids`` as a device tensor (a host list would need a host-to-device copy inside the
+    capture); its EOS check is one read-back, made by every call outside a capture -- the warm-up pass included -- and skipped while the
+    stream captures."""
+    from .Constants import EOS_WORD
+    eos = vocab2id[EOS_WORD]
+    try:
+        m = None if isinstance(min_length, bool) else operator.index(min_length)
+    except TypeError:
+        m = None
+    if m is None or m < 0:
+        raise ValueError("min_length must be an integer >= 0 (0 = off)")
+    if max_target_length is not None and m > max_target_length - 1:
+        raise ValueError("min_length %d leaves no position for EOS within max_target_length %d" % (m, max_target_length))
+    try:
+        alpha = None if isinstance(length_penalty, bool) else float(length_penalty)
+    except (TypeError, ValueError):
+        alpha = None
+    if alpha is None or not (alpha >= 0.0) or alpha == float("inf"):
+        raise ValueError("length_penalty must be a finite float >= 0 (1.0 = cost / length)")
+    banned = None
+    if banned_ids is not None:
+        try:
+            banned = banned_ids.detach() if torch.is_tensor(banned_ids) else torch.as_tensor(banned_ids)
+        except (TypeError, ValueError, RuntimeError):
+            raise ValueError("banned_ids must be an integer tensor or sequence [K] or [B, K]")
+        if banned.numel() == 0 and banned.dim() <= 2:
+            banned = None
+        else:
+            if banned.dtype not in (torch.int64, torch.int32, torch.int16, torch.int8, torch.uint8):
+                raise ValueError("banned_ids must hold integers, not %s" % banned.dtype)
+            if banned.dim() not in (1, 2) or (banned.dim() == 2 and banned.shape[0] != B):
+                raise ValueError("banned_ids must be [K] or [B, K] with the batch's B = %d, not %s" % (B, list(banned.shape)))
+            if banned.shape[-1] > ops.RULES_MAX_BANNED:
+                raise ValueError("banned_ids: at most %d ids per item (got %d)" % (ops.RULES_MAX_BANNED, banned.shape[-1]))
+            # (one read-back for a device tensor; a capturing stream cannot read back, and the warm-up pass a capture needs has made the check)
+            if not (banned.is_cuda and torch.cuda.is_current_stream_capturing()) and bool(banned.eq(eos).any()):
+                raise ValueError("banned_ids must not hold EOS (%d): use min_length to keep an answer from ending" % eos)
+            banned = banned.to(device=device, dtype=torch.int32).contiguous()
+    return dict(min_length=m, banned=banned, length_penalty=alpha, eos=eos, on=bool(m or banned is not None))
+
+
 class _DecodeMode:
     """What differs between the decoding modes of ``PointerDecoderCore._decode``: how a step's head becomes the next ids [R, 1]
     (``fused_step`` from the f32 logits, mixing logits, sorted source map and copy weights [R, len_k]; ``unfused_step`` from the unfused
@@ -132,10 +180,25 @@ class _DecodeMode:
     consecutive: row b * N + n is candidate n (beam slot, sample) of item b."""
     counter = None  # the decoder attribute that receives the number of steps the pass ran: last_greedy_steps / last_beam_steps / last_sample_steps
     ngram = 0  # no_repeat_ngram (K32): 0 = off, the launches of a pass without it
+    rules = None  # min_length / banned ids (an ops.RowRules at t = 0): None = off, the launches of a pass without them
 
-    def _banned_copy(self, dist, hist, t, eos):
-        """The unfused head with the ban on: a float copy of the newest position's distribution with the banned entries zeroed."""
-        return ops.ngram_ban_(dist[:, -1].detach().to(torch.float32, copy=True), hist, t, self.ngram, eos)
+    def _set_rules(self, rules, rows_per_item):
+        """``rules``: what ``decode_rules_param`` returned (or None).  The pass's RowRules, made once; a step takes ``_rules_at(t)``."""
+        if rules is not None and rules["on"]:
+            self.rules = ops.row_rules(rules["eos"], rules["min_length"], rules["banned"], rows_per_item)
+
+    def _rules_at(self, t):
+        return None if self.rules is None else self.rules._replace(t=t)
+
+    def _banned_copy(self, dist, hist, t, eos, ended=None):
+        """The unfused head with the ban or the rules on: a float copy of the newest position's distribution with the banned entries zeroed (K32
+        first, then the rules, as the fused heads do)."""
+        row = dist[:, -1].detach().to(torch.float32, copy=True)
+        if self.ngram:
+            ops.ngram_ban_(row, hist, t, self.ngram, eos, ended)
+        if self.rules is not None:
+            ops.row_rules_(row, self._rules_at(t), ended)
+        return row
 
     def start(self, capturing, self_kvs, hist_valid):
         pass
@@ -154,8 +217,9 @@ class _GreedyMode(_DecodeMode):
     the last one.  -> (dec_out, gen, dist of the last step, answer [B, T], PAD behind a short pass)."""
     counter = "last_greedy_steps"
 
-    def __init__(self, decoder, B, T, dev, ngram=0):
+    def __init__(self, decoder, B, T, dev, ngram=0, rules=None):
         self.T, self.V, self.eos, self.ngram = T, decoder.tgt_vocab_size, decoder.eos_id, ngram
+        self._set_rules(rules, 1)
         self.hist = torch.zeros(B, T, dtype=torch.int32, device=dev) if ngram else None  # K23 appends its argmax at [:, t]
         self.finished = None if self.eos is None else torch.zeros(B, dtype=torch.bool, device=dev)
         self.picked, self.gen, self.dist = [], None, None
@@ -166,15 +230,19 @@ class _GreedyMode(_DecodeMode):
     def fused_step(self, t, logits, mix_logits, source_map, copies):
         want = t == self.T - 1 or self.any_step_may_be_last
         ban = (self.hist, t, self.ngram, self.eos) if self.ngram else None
-        gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want, ban=ban)
+        if self.rules is None:
+            gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want, ban=ban)
+        else:
+            gen, dist, ids = ops.pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=want, want_dist=want, ban=ban, rules=self._rules_at(t))
         self.gen, self.dist = (gen.view(-1, 1, self.V), dist.view(-1, 1, self.V)) if want else (None, None)
         return self._emit(ids.unsqueeze(1))
 
     def unfused_step(self, t, gen, dist):
-        if self.ngram:  # dist is returned as the row after the ban, as K23 returns it
+        if self.ngram or self.rules is not None:  # dist is returned as the row after the ban and the rules, as K23 returns it
             row = self._banned_copy(dist, self.hist, t, self.eos)
             ids = ops.row_argmax(row)[0]
-            self.hist[:, t] = ids
+            if self.ngram:
+                self.hist[:, t] = ids
             self.gen, self.dist = gen, row.unsqueeze(1)
             return self._emit(ids.unsqueeze(1))
         self.gen, self.dist = gen, dist
@@ -206,9 +274,13 @@ class _BeamMode(_DecodeMode):
     slot is alive.  -> (dec_out of the last step's rows, None, None, answer [B, T], beam_answers [B, W, T], beam_scores [B, W])."""
     counter = "last_beam_steps"
 
-    def __init__(self, decoder, B, W, T, dev, ngram=0):
+    def __init__(self, decoder, B, W, T, dev, ngram=0, rules=None):
         self.W, self.eos, self.ngram = W, decoder.beam_eos_id, ngram
-        self.state = ops.BeamState(B, W, T, dev, flat=bool(ngram))  # the flat history: a slot's history is its hypothesis, K25 carries it along
+        self._set_rules(rules, W)
+        self.alpha = 1.0 if rules is None else rules["length_penalty"]
+        # the flat history: a slot's history is its hypothesis, K25 carries it along.  Any rule selects it too: that form of K25 holds a candidate
+        # of probability 0 dead (a zeroed EOS or banned id never enters a hypothesis) and is the one that takes the length penalty
+        self.state = ops.BeamState(B, W, T, dev, flat=bool(ngram) or self.rules is not None or self.alpha != 1.0)
 
     def start(self, capturing, self_kvs, hist_valid):
         spare = [[torch.zeros_like(c) for c in layers] for layers in self_kvs]
@@ -217,15 +289,22 @@ class _BeamMode(_DecodeMode):
 
     def fused_step(self, t, logits, mix_logits, source_map, copies):
         ban = (self.state.flat_rows(t), t, self.ngram, self.eos) if self.ngram else None
-        _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W, ban=ban)
+        if self.rules is None:
+            _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W, ban=ban)
+        else:
+            _, _, cand_p, cand_id = ops.pointer_head_topk(logits, mix_logits, source_map, copies, self.W, ban=ban, rules=self._rules_at(t))
         return self._advance(t, cand_p, cand_id)
 
     def unfused_step(self, t, gen, dist):
-        row = self._banned_copy(dist, self.state.flat_rows(t), t, self.eos) if self.ngram else dist[:, -1].detach().float()
+        ruled = self.ngram or self.rules is not None
+        row = self._banned_copy(dist, self.state.flat_rows(t) if self.ngram else None, t, self.eos) if ruled else dist[:, -1].detach().float()
         return self._advance(t, *torch.topk(row, self.W, dim=-1))
 
     def _advance(self, t, cand_p, cand_id):
-        ops.beam_advance(self.state, cand_p, cand_id, t, self.eos)
+        if self.alpha == 1.0:
+            ops.beam_advance(self.state, cand_p, cand_id, t, self.eos)
+        else:
+            ops.beam_advance(self.state, cand_p, cand_id, t, self.eos, length_penalty=self.alpha)
         return self.state.token.view(-1, 1)
 
     def after_step(self, t, self_kvs, hist_valid):
@@ -256,9 +335,10 @@ class _SampleMode(_DecodeMode):
     -> (dec_out of the last step's rows, None, None, answer [B, T], samples [B, N, T], sample_probs [B, N, T], sample_scores [B, N])."""
     counter = "last_sample_steps"
 
-    def __init__(self, B, T, dev, params, ngram=0):
+    def __init__(self, B, T, dev, params, ngram=0, rules=None):
         self.B, self.N, self.T, self.R, self.pad = B, int(params["num_samples"]), T, B * int(params["num_samples"]), params["pad"]
         self.ngram = ngram
+        self._set_rules(rules, self.N)
         self.hist = torch.zeros(self.R, T, dtype=torch.int32, device=dev) if ngram else None  # K28 appends the emitted id at [:, t]
         self.seed, self.uniforms = params.get("seed"), params.get("uniforms")
         if self.uniforms is not None and tuple(self.uniforms.shape) != (T, self.R):
@@ -272,6 +352,8 @@ class _SampleMode(_DecodeMode):
         rng = None if u is not None else config.next_rng(self.R) if self.seed is None else (int(self.seed), t * self.R, None)
         if self.ngram:  # (K28 applies the ban to either row source, the unfused ``dist_in`` included)
             kw["ban"] = (self.hist, t, self.ngram)
+        if self.rules is not None:  # (likewise; a row that has ended is left alone)
+            kw["rules"] = self._rules_at(t)
         _, _, tok, p = ops.pointer_head_sample(*head, self.ended, t == 0, t == self.T - 1, *self.draw, rng=rng, uniforms=u, **kw)
         self.picked.append(tok.unsqueeze(1))
         self.probs.append(p.unsqueeze(1))
@@ -520,9 +602,10 @@ class PointerDecoderCore(nn.Module):
         return dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
 
     def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-             score_index, feature_of=None, no_repeat_ngram=0):
+             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None):
         """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
-        (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) applies to the three decoding modes only."""
+        (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) and ``decode_rules`` (what ``decode_rules_param`` returned: min_length,
+        banned ids, the beam length penalty) apply to the three decoding modes only."""
         B, dev = source_map.size(0), encode_memories[0].device
         source_map = self._sorted(source_map)
         mems = [m.reshape(B, -1, self.hidden_size) for m in encode_memories]
@@ -542,18 +625,28 @@ class PointerDecoderCore(nn.Module):
         ngram = no_repeat_ngram_param(no_repeat_ngram, T)
         if ngram and not ops.ngram_ban_supported():
             raise RuntimeError("no_repeat_ngram: this build of the library lacks the n-gram ban (CASE_FEAT_NGRAM_BAN)")
+        rules = decode_rules
+        if rules is not None and not (rules["on"] or rules["length_penalty"] != 1.0):
+            rules = None  # every rule off: the launches of a pass without the argument
+        if rules is not None:
+            if not ops.decode_rules_supported():
+                raise RuntimeError("min_length / banned_ids / length_penalty: this build of the library lacks the decoding rules (CASE_FEAT_DECODE_RULES)")
+            if rules["min_length"] > T - 1:
+                raise ValueError("min_length %d leaves no position for EOS within max_target_length %d" % (rules["min_length"], T))
+            if rules["banned"] is not None and (rules["banned"].device != dev or (rules["banned"].dim() == 2 and rules["banned"].shape[0] != B)):
+                raise ValueError("banned_ids must be on the batch's device and [K] or [B, K] with the batch's B = %d" % B)
         if beam_width:
             W = int(beam_width)
             if not ops.beam_supported(W):
                 raise RuntimeError("beam search: width %d is outside what the beam kernels are built for (1 .. 8)" % W)
-            mode, n = _BeamMode(self, B, W, T, dev, ngram), W
+            mode, n = _BeamMode(self, B, W, T, dev, ngram, rules), W
         elif sampling:
             if not ops.sample_supported(self.tgt_vocab_size):
                 raise RuntimeError("sampled decoding: this build of the library cannot draw from a vocabulary of %d (CASE_FEAT_SAMPLE_DECODE, "
                                    "CASE_FEAT_POINTER_HEAD_WIDE)" % self.tgt_vocab_size)
-            mode, n = _SampleMode(B, T, dev, sampling, ngram), int(sampling["num_samples"])
+            mode, n = _SampleMode(B, T, dev, sampling, ngram, rules), int(sampling["num_samples"])
         else:
-            mode, n = _GreedyMode(self, B, T, dev, ngram), 1
+            mode, n = _GreedyMode(self, B, T, dev, ngram, rules), 1
         # beam search repeats its rows at width 1 too
         return self._decode(mode, *self._per_item(n, mems, valid, weights, source_map, feat, unit_too=bool(beam_width)), BOS, T)
 
@@ -622,8 +715,8 @@ class TransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0):
+                no_repeat_ngram=0, decode_rules=None):
         if isinstance(source_maps, (list, tuple)):
             source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
         return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules)

@@ -515,6 +515,42 @@ __device__ __forceinline__ void ngram_ban_row(float* row, const int64_t V, const
   __syncthreads();
 }
 
+// ---- the decoding rules behind K32: min_length and banned ids ---------------------------------------------------------------------------------
+// At step t (= the tokens the row has emitted) row[eos] becomes 0.0 while t < min_len, and row[v] becomes 0.0 for every v of the row's item's
+// list bad[0 .. nbad) (the list of item r / rows_per_item: bad + item * bad_stride; stride 0 = one list for every item).  Ids outside [0, V) are
+// ignored (-1 pads a list), duplicates are harmless, nothing is renormalised; a row left all zero behaves as an all-zero row does (id 0,
+// value 0).  Unlike K32 there is no "history holds eos" clause and no step bound.  The `_rules` instances take the ban's operands too, with
+// n = 0 (and hist == nullptr) allowed: no ban, and nothing is appended.
+constexpr int RR_MAX_BAD = 256;
+struct RuleArgs {
+  const int32_t* bad;  // [nbad] or [items, nbad] int32, null with nbad = 0
+  int64_t eos, bad_stride, rows_per_item;
+  int t, min_len, nbad;
+};
+struct RuleBanArgs : BanArgs {
+  RuleArgs rl;
+};
+template <bool RULES>
+struct TailArgs {
+  typedef BanArgs type;
+};
+template <>
+struct TailArgs<true> {
+  typedef RuleBanArgs type;
+};
+
+// Every thread of the block calls it; `row` is readable by every thread before and after (the barrier inside).  Plain stores of 0.f; several
+// threads may write the same zero.
+__device__ __forceinline__ void row_rules_row(float* row, const int64_t V, const RuleArgs& rl, const int64_t r) {
+  const int32_t* __restrict__ bad = rl.bad + (r / rl.rows_per_item) * rl.bad_stride;
+  if (threadIdx.x == 0 && rl.t < rl.min_len && rl.eos >= 0 && rl.eos < V) row[rl.eos] = 0.f;
+  for (int i = threadIdx.x; i < rl.nbad; i += blockDim.x) {
+    const int v = bad[i];
+    if (v >= 0 && (int64_t)v < V) row[v] = 0.f;
+  }
+  __syncthreads();
+}
+
 // the row build shared by K23 and its beam form: row[0 .. V) = pm_0 softmax(logits) + the pointer mass of the sorted source keys (gen written
 // on the way when asked for).  Ends behind a barrier: every thread may read the whole row.
 // WIDE (the row in device memory): the exponentials are formed from the logits again where the LDS form reads them back from the row -- the
@@ -601,8 +637,9 @@ __device__ __forceinline__ void pointer_head_build_row(const HeadArgs& a, float*
 
 // WIDE: the row lives in a.row_ws (device memory) and LDS holds the staging and scratch only.  A workgroup reads back its own global stores
 // behind __syncthreads() (one CU, one L1); no row is shared between workgroups.
-template <bool BAN, bool WIDE = false>
-__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a, const BanArgs nb) {
+// RULES (the `_rules` instances; BAN is set there too): `nb` carries the rules behind the ban's operands, and n = 0 / hist == nullptr means no ban.
+template <bool BAN, bool WIDE = false, bool RULES = false>
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const HeadArgs a, const typename TailArgs<RULES>::type nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   float* row = WIDE ? a.row_ws + (int64_t)blockIdx.x * a.row_stride : ph_smem;  // [V]
   uint32_t* tk = reinterpret_cast<uint32_t*>(WIDE ? ph_smem : ph_smem + ((a.V + 3) & ~(int64_t)3));  // [PH_THREADS + 1]
@@ -613,7 +650,8 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
   const int64_t b = blockIdx.x, V = a.V;
   const int tid = threadIdx.x;
   pointer_head_build_row<WIDE>(a, row, tk, tv, red, b);
-  if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));
+  if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));  // (n = 0: returns before it reads)
+  if constexpr (RULES) row_rules_row(row, V, nb.rl, b);
   // outputs: the distribution row and its argmax (lowest index on ties)
   float bv = -INFINITY;
   int64_t bi = V;
@@ -647,7 +685,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
       }
     a.ids[b] = bi < V ? bi : 0;
     if (a.top) a.top[b] = bv;
-    if constexpr (BAN) nb.hist[b * nb.Tmax + nb.t] = (int32_t)(bi < V ? bi : 0);
+    if constexpr (BAN) {
+      if (!RULES || nb.hist) nb.hist[b * nb.Tmax + nb.t] = (int32_t)(bi < V ? bi : 0);
+    }
   }
 }
 
@@ -657,9 +697,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_decode_kernel(const H
 // W largest entries with the lowest id first on ties, whatever the scheduling; round 0 is K23's argmax comparison for comparison, so W = 1
 // returns K23's id and value bit for bit.  Scratch on top of K23's: two words for the previous winner.
 constexpr int PH_MAX_W = 8;
-template <bool BAN, bool WIDE = false>
+template <bool BAN, bool WIDE = false, bool RULES = false>
 __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const HeadArgs a, float* __restrict__ cand_p, int64_t* __restrict__ cand_id,
-                                                                       const int W, const BanArgs nb) {
+                                                                       const int W, const typename TailArgs<RULES>::type nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   float* row = WIDE ? a.row_ws + (int64_t)blockIdx.x * a.row_stride : ph_smem;
   uint32_t* tk = reinterpret_cast<uint32_t*>(WIDE ? ph_smem : ph_smem + ((a.V + 3) & ~(int64_t)3));
@@ -673,6 +713,7 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_beam_kernel(const Hea
   const int tid = threadIdx.x;
   pointer_head_build_row<WIDE>(a, row, tk, tv, red, b);
   if constexpr (BAN) ngram_ban_row(row, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, reinterpret_cast<int*>(tv));  // (K25 appends: a slot's history is its hypothesis)
+  if constexpr (RULES) row_rules_row(row, V, nb.rl, b);
   float pv = INFINITY;  // the previous round's winner: round 0 admits every entry
   int64_t pi = -1;
   for (int r = 0; r < W; ++r) {
@@ -929,8 +970,8 @@ __device__ __forceinline__ float sample_scan64(float x, int lane) {  // inclusiv
 
 // WIDE: the row in a.row_ws, or -- a ready distribution with no workspace given (the host's choice: 16-byte aligned rows, no ban) -- `dist_in`
 // itself, which no pass writes.  The quads read up to three floats behind V inside the row's stride; those entries are never kept.
-template <bool BAN, bool WIDE = false>
-__global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s, const BanArgs nb) {
+template <bool BAN, bool WIDE = false, bool RULES = false>
+__global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const HeadArgs a, const SampleArgs s, const typename TailArgs<RULES>::type nb) {
   extern __shared__ __attribute__((aligned(16))) float ph_smem[];
   const bool in_place = WIDE && !a.row_ws;  // (block-uniform)
   float* row = !WIDE ? ph_smem : in_place ? const_cast<float*>(s.dist_in) + (int64_t)blockIdx.x * a.V : a.row_ws + (int64_t)blockIdx.x * a.row_stride;
@@ -953,6 +994,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
   }
   if constexpr (BAN) {
     if (!s.ended[b]) ngram_ban_row(row, a.V, nb.hist + b * nb.Tmax, nb.t, nb.n, s.eos, reinterpret_cast<int*>(tv));  // (block-uniform; tid 0 rewrites ended[b] behind the last barrier)
+  }
+  if constexpr (RULES) {
+    if (!s.ended[b]) row_rules_row(row, a.V, nb.rl, b);  // (block-uniform, as above; an ended row keeps emitting PAD with probability 1)
   }
   float pmax = 0.f;
   for (int i = tid; i < V; i += PH_THREADS) {
@@ -1059,7 +1103,9 @@ __global__ __launch_bounds__(PH_THREADS) void pointer_head_sample_kernel(const H
     else if (s.last) emit = e ? s.pad : s.eos;
     else emit = e ? s.pad : (int64_t)x;
     s.ids[b] = emit;
-    if constexpr (BAN) nb.hist[b * nb.Tmax + nb.t] = (int32_t)emit;
+    if constexpr (BAN) {
+      if (!RULES || nb.hist) nb.hist[b * nb.Tmax + nb.t] = (int32_t)emit;
+    }
     s.prob[b] = e ? 1.f : row[x];
     s.ended[b] = (uint8_t)(e || this_end);
   }
@@ -1071,6 +1117,13 @@ __global__ __launch_bounds__(64) void ngram_ban_kernel(float* __restrict__ dist,
   const int64_t b = blockIdx.x;
   if (ended && ended[b]) return;
   ngram_ban_row(dist + b * V, V, nb.hist + b * nb.Tmax, nb.t, nb.n, nb.eos, stage);
+}
+
+// the decoding rules on a distribution row in global memory (the unfused head): one wave per row
+__global__ __launch_bounds__(64) void row_rules_kernel(float* __restrict__ dist, const uint8_t* __restrict__ ended, const int64_t V, const RuleArgs rl) {
+  const int64_t b = blockIdx.x;
+  if (ended && ended[b]) return;
+  row_rules_row(dist + b * V, V, rl, b);
 }
 
 // ---- K29: the head of a teacher-forced SCORING pass: one probability per row, no vocabulary row -------------------------------------------
@@ -1532,10 +1585,10 @@ static int pointer_head_ban_opt(BanArgs& nb, bool& ban, const char* who, const i
   return ban ? pointer_head_ban(nb, who, hist, Tmax, t, n, eos) : CASE_OK;
 }
 
-template <bool BAN>
+template <bool BAN, bool RULES = false>
 static int pointer_head_decode_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
                                            const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids,
-                                           float* top, int64_t B, int64_t V, int64_t S, float* row_ws, int64_t row_stride, const BanArgs& nb,
+                                           float* top, int64_t B, int64_t V, int64_t S, float* row_ws, int64_t row_stride, const typename TailArgs<RULES>::type& nb,
                                            case_stream_t stream) {
   CASE_REQUIRE(ids, "%s: bad argument", who);
   HeadArgs a;
@@ -1545,14 +1598,14 @@ static int pointer_head_decode_wide_launch(const char* who, const float* logits,
   if (rc != CASE_OK) return rc;
   a.ids = ids;
   a.top = top;
-  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, true>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, nb);
+  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, true, RULES>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, nb);
   return case_check_launch(who);
 }
 
-template <bool BAN>
+template <bool BAN, bool RULES = false>
 static int pointer_head_decode_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                       const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
-                                      int64_t S, const BanArgs& nb, case_stream_t stream) {
+                                      int64_t S, const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
   CASE_REQUIRE(ids, "%s: bad argument", who);
   HeadArgs a;
   int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
@@ -1560,9 +1613,9 @@ static int pointer_head_decode_launch(const char* who, const float* logits, cons
   a.ids = ids;
   a.top = top;
   static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel<BAN>), attr, who);
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel<BAN, false, RULES>), attr, who);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_decode_kernel<BAN>, dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, nb);
+  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, false, RULES>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, nb);
   return case_check_launch(who);
 }
 
@@ -1599,11 +1652,11 @@ extern "C" int case_pointer_head_decode_wide(const float* logits, const float* m
                                                       row_stride, nb, stream);
 }
 
-template <bool BAN>
+template <bool BAN, bool RULES = false>
 static int pointer_head_beam_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
                                          const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p,
                                          int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride,
-                                         const BanArgs& nb, case_stream_t stream) {
+                                         const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
   CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
   if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
   HeadArgs a;
@@ -1611,7 +1664,7 @@ static int pointer_head_beam_wide_launch(const char* who, const float* logits, c
   if (rc != CASE_OK) return rc;
   rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, true>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, cand_p,
+  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, true, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, cand_p,
                      cand_id, (int)W, nb);
   return case_check_launch(who);
 }
@@ -1631,19 +1684,19 @@ extern "C" int case_pointer_head_beam_wide(const float* logits, const float* mix
                                                     row_stride, nb, stream);
 }
 
-template <bool BAN>
+template <bool BAN, bool RULES = false>
 static int pointer_head_beam_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                     const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V,
-                                    int64_t S, int32_t W, const BanArgs& nb, case_stream_t stream) {
+                                    int64_t S, int32_t W, const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
   CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
   if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
   HeadArgs a;
   int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
   if (rc != CASE_OK) return rc;
   static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel<BAN>), attr, who);
+  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel<BAN, false, RULES>), attr, who);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_beam_kernel<BAN>, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id,
+  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, false, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id,
                      (int)W, nb);
   return case_check_launch(who);
 }
@@ -1666,12 +1719,12 @@ extern "C" int case_pointer_head_beam_ban(const float* logits, const float* mix_
                                         W, nb, stream);
 }
 
-template <bool BAN, bool WIDE = false>
+template <bool BAN, bool WIDE = false, bool RULES = false>
 static int pointer_head_sample_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
                                       const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
                                       uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
                                       float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad,
-                                      int32_t first, int32_t last, const BanArgs& nb, case_stream_t stream, float* row_ws = nullptr,
+                                      int32_t first, int32_t last, const typename TailArgs<RULES>::type& nb, case_stream_t stream, float* row_ws = nullptr,
                                       int64_t row_stride = 0) {
   CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "%s: bad argument", who);
   CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f, "%s: temperature must be > 0, top_k >= 0 and top_p in (0, 1]", who);
@@ -1713,13 +1766,13 @@ static int pointer_head_sample_launch(const char* who, const float* logits, cons
   s.first = first;
   s.last = last;
   if constexpr (WIDE) {
-    hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, true>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, s, nb);
+    hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, true, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, s, nb);
     return case_check_launch(who);
   }
   static bool attr = false;
-  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel<BAN>), attr, who);
+  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel<BAN, false, RULES>), attr, who);
   if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(pointer_head_sample_kernel<BAN>, dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s, nb);
+  hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, false, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s, nb);
   return case_check_launch(who);
 }
 
@@ -1775,6 +1828,127 @@ extern "C" int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* e
   if (rc != CASE_OK) return rc;
   hipLaunchKernelGGL(ngram_ban_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, dist, ended, V, nb);
   return case_check_launch("case_ngram_ban");
+}
+
+// ---- the decoding rules (CASE_FEAT_DECODE_RULES): the `_rules` forms of the heads and case_row_rules ------------------------------------------------
+static int pointer_head_rule_args(RuleArgs& rl, const char* who, int64_t rows, int64_t t, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
+                                  int64_t banned_stride, int64_t rows_per_item) {
+  CASE_REQUIRE(t >= 0 && t < (1ll << 31) && min_length >= 0 && K >= 0 && (K == 0 || banned) && rows_per_item >= 1 &&
+                   (banned_stride == 0 || (banned_stride == K && rows % rows_per_item == 0)),
+               "%s: bad rule argument (t >= 0, min_length >= 0, banned [K] with stride 0 or [rows / rows_per_item, K] with stride K)", who);
+  if (K > RR_MAX_BAD) return case_set_error(CASE_E_UNSUPPORTED, "%s: at most %d banned ids per item (got %d)", who, RR_MAX_BAD, K);
+  rl.bad = K ? banned : nullptr;
+  rl.eos = eos;
+  rl.bad_stride = K ? banned_stride : 0;
+  rl.rows_per_item = rows_per_item;
+  rl.t = (int)t;
+  rl.min_len = (int)min_length;
+  rl.nbad = (int)K;
+  return CASE_OK;
+}
+
+// the ban's operands (hist == NULL or n == 0: no ban, as in the wide forms) and the rules into one kernel argument
+static int pointer_head_rules(RuleBanArgs& nb, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t rows,
+                              int64_t eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item) {
+  nb = RuleBanArgs();
+  if (hist != nullptr && n != 0) {
+    const int rc = pointer_head_ban(nb, who, hist, Tmax, t, n, ban_eos);
+    if (rc != CASE_OK) return rc;
+  }
+  return pointer_head_rule_args(nb.rl, who, rows, t, eos, min_length, banned, K, banned_stride, rows_per_item);
+}
+
+extern "C" int case_pointer_head_decode_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                              const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                              int64_t V, int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t eos,
+                                              int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item,
+                                              case_stream_t stream) {
+  const char* who = "case_pointer_head_decode_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, B, eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_decode_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, nb, stream);
+}
+
+extern "C" int case_pointer_head_decode_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                                   const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                                   int64_t V, int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t,
+                                                   int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
+                                                   int64_t banned_stride, int64_t rows_per_item, case_stream_t stream) {
+  const char* who = "case_pointer_head_decode_wide_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, B, eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_decode_wide_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws, row_stride,
+                                                     nb, stream);
+}
+
+extern "C" int case_pointer_head_beam_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                            const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                            int64_t V, int64_t S, int32_t W, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos,
+                                            int64_t eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
+                                            int64_t rows_per_item, case_stream_t stream) {
+  const char* who = "case_pointer_head_beam_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, R, eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_beam_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, nb, stream);
+}
+
+extern "C" int case_pointer_head_beam_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                                 const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                                 int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
+                                                 int64_t t, int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
+                                                 int64_t banned_stride, int64_t rows_per_item, case_stream_t stream) {
+  const char* who = "case_pointer_head_beam_wide_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, R, eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_beam_wide_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
+                                                   row_stride, nb, stream);
+}
+
+extern "C" int case_pointer_head_sample_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                              const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                              float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
+                                              int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
+                                              int64_t unk, int64_t pad, int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
+                                              int64_t rule_eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
+                                              int64_t rows_per_item, case_stream_t stream) {
+  const char* who = "case_pointer_head_sample_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, eos, R, rule_eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_sample_launch<true, false, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
+                                                       R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream);
+}
+
+extern "C" int case_pointer_head_sample_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                                   const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                                   float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S,
+                                                   float temperature, int32_t top_k, float top_p, uint64_t seed, uint64_t offset,
+                                                   const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first, int32_t last,
+                                                   float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
+                                                   int64_t rule_eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
+                                                   int64_t rows_per_item, case_stream_t stream) {
+  const char* who = "case_pointer_head_sample_wide_rules";
+  RuleBanArgs nb;
+  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, eos, R, rule_eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  return pointer_head_sample_launch<true, true, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
+                                                      R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
+                                                      row_ws, row_stride);
+}
+
+// the rules as a launch of their own (the unfused head): one wave per row zeroes the entries of dist [R, V] in place
+extern "C" int case_row_rules(float* dist, const uint8_t* ended, int64_t R, int64_t V, int64_t t, int64_t eos, int32_t min_length,
+                              const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item, case_stream_t stream) {
+  CASE_REQUIRE(dist && R > 0 && R < (1ll << 31) && V > 0, "case_row_rules: bad argument");
+  RuleArgs rl;
+  const int rc = pointer_head_rule_args(rl, "case_row_rules", R, t, eos, min_length, banned, K, banned_stride, rows_per_item);
+  if (rc != CASE_OK) return rc;
+  hipLaunchKernelGGL(row_rules_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, dist, ended, V, rl);
+  return case_check_launch("case_row_rules");
 }
 
 extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,

@@ -20,15 +20,18 @@ constexpr int BEAM_MAX_W = 8;
 // (a copy by parent cannot run in place): new[b, w, 0 .. t) = old[b, parent, 0 .. t), new[b, w, t] = the slot's token -- W t <= 2048 ints per
 // item.  With the ban on, a candidate of probability exactly 0 (a banned entry that reached the top W) is dead: it can neither take a slot nor
 // retire into the pool.
-template <bool FLAT>
-__global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restrict__ cand_p, const int64_t* __restrict__ cand_id,
-                                                          uint8_t* __restrict__ alive, float* __restrict__ cum, int32_t* __restrict__ len,
-                                                          int32_t* __restrict__ parent, int64_t* __restrict__ token,
-                                                          int32_t* __restrict__ hist_parent, int64_t* __restrict__ hist_token,
-                                                          float* __restrict__ fin_key, int32_t* __restrict__ fin_step, int32_t* __restrict__ fin_slot,
-                                                          const int t, const int T, const int64_t B, const int W, const int64_t eos,
-                                                          const int32_t* __restrict__ flat_old, int32_t* __restrict__ flat_new,
-                                                          const int64_t Tmax) {
+// ALPHA (the length penalty): key = cost / (len[slot] + 1)^alpha, powf in f32, once per live candidate; a retiring hypothesis takes its
+// candidate's key as it is (the same cost and length), so the finished pool is ranked by the same formula.  Without ALPHA the key is the
+// division above and the code that of the kernels below, instruction for instruction.
+template <bool FLAT, bool ALPHA>
+__device__ __forceinline__ void beam_advance_body(const float* __restrict__ cand_p, const int64_t* __restrict__ cand_id,
+                                                  uint8_t* __restrict__ alive, float* __restrict__ cum, int32_t* __restrict__ len,
+                                                  int32_t* __restrict__ parent, int64_t* __restrict__ token,
+                                                  int32_t* __restrict__ hist_parent, int64_t* __restrict__ hist_token,
+                                                  float* __restrict__ fin_key, int32_t* __restrict__ fin_step, int32_t* __restrict__ fin_slot,
+                                                  const int t, const int T, const int64_t B, const int W, const int64_t eos,
+                                                  const int32_t* __restrict__ flat_old, int32_t* __restrict__ flat_new,
+                                                  const int64_t Tmax, const float alpha) {
   __shared__ int src[BEAM_MAX_W];
   __shared__ int n_par[BEAM_MAX_W], n_tok[BEAM_MAX_W];
   __shared__ float s_key[64], s_cum[64];
@@ -50,7 +53,7 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restric
       const float p = cand_p[row * W + (lane - slot * W)];
       if (!(FLAT && p == 0.f)) {
         c = cum[row] - logf(p + 1e-10f);
-        key = c / (float)(plen + 1);
+        key = ALPHA ? c / powf((float)(plen + 1), alpha) : c / (float)(plen + 1);
       }
     }
   }
@@ -146,6 +149,32 @@ __global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restric
   }
 }
 
+template <bool FLAT>
+__global__ __launch_bounds__(64) void beam_advance_kernel(const float* __restrict__ cand_p, const int64_t* __restrict__ cand_id,
+                                                          uint8_t* __restrict__ alive, float* __restrict__ cum, int32_t* __restrict__ len,
+                                                          int32_t* __restrict__ parent, int64_t* __restrict__ token,
+                                                          int32_t* __restrict__ hist_parent, int64_t* __restrict__ hist_token,
+                                                          float* __restrict__ fin_key, int32_t* __restrict__ fin_step, int32_t* __restrict__ fin_slot,
+                                                          const int t, const int T, const int64_t B, const int W, const int64_t eos,
+                                                          const int32_t* __restrict__ flat_old, int32_t* __restrict__ flat_new,
+                                                          const int64_t Tmax) {
+  beam_advance_body<FLAT, false>(cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot, t, T, B, W, eos,
+                                 flat_old, flat_new, Tmax, 1.f);
+}
+
+// K25 with the length penalty (flat history)
+__global__ __launch_bounds__(64) void beam_advance_alpha_kernel(const float* __restrict__ cand_p, const int64_t* __restrict__ cand_id,
+                                                                uint8_t* __restrict__ alive, float* __restrict__ cum, int32_t* __restrict__ len,
+                                                                int32_t* __restrict__ parent, int64_t* __restrict__ token,
+                                                                int32_t* __restrict__ hist_parent, int64_t* __restrict__ hist_token,
+                                                                float* __restrict__ fin_key, int32_t* __restrict__ fin_step,
+                                                                int32_t* __restrict__ fin_slot, const int t, const int T, const int64_t B, const int W,
+                                                                const int64_t eos, const int32_t* __restrict__ flat_old,
+                                                                int32_t* __restrict__ flat_new, const int64_t Tmax, const float alpha) {
+  beam_advance_body<true, true>(cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot, t, T, B, W, eos,
+                                flat_old, flat_new, Tmax, alpha);
+}
+
 // ---- K26 -------------------------------------------------------------------------------------------------------------------------
 // dst[l][b * W + w, 0 .. t] = src[l][b * W + parent[b, w], 0 .. t] for every layer l of the table, 16 bytes per lane and access; the last
 // grid row copies the prefix validity bytes.  Source and destination are different buffers (the caller ping-pongs).
@@ -229,6 +258,24 @@ extern "C" int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id
   hipLaunchKernelGGL(beam_advance_kernel<true>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
                      hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax);
   return case_check_launch("case_beam_advance_ban");
+}
+
+// K25 with the length penalty alpha (CASE_FEAT_DECODE_RULES): the flat-history form; alpha == 1 is case_beam_advance_ban's launch itself
+extern "C" int case_beam_advance_rules(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
+                                       int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step,
+                                       int32_t* fin_slot, int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, const int32_t* flat_old,
+                                       int32_t* flat_new, int64_t Tmax, float length_penalty, case_stream_t stream) {
+  CASE_REQUIRE(length_penalty >= 0.f && length_penalty < INFINITY, "case_beam_advance_rules: the length penalty must be a finite float >= 0");
+  if (length_penalty == 1.f)
+    return case_beam_advance_ban(cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot, t, T, B, W, eos,
+                                 flat_old, flat_new, Tmax, stream);
+  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
+                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T && flat_old && flat_new && flat_old != flat_new && t < Tmax,
+               "case_beam_advance_rules: bad argument");
+  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance_rules: width %d outside 1 .. %d", W, BEAM_MAX_W);
+  hipLaunchKernelGGL(beam_advance_alpha_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
+                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax, length_penalty);
+  return case_check_launch("case_beam_advance_rules");
 }
 
 extern "C" int case_beam_gather(const void* const* src, void* const* dst, int32_t nlayers, const int32_t* parent, const uint8_t* valid_src,

@@ -4,6 +4,7 @@ PyTorch is used here for device memory (caching allocator), streams and the auto
 arithmetic pass over an activation is a kernel of libcase_hip.so launched through ``_abi`` on the current
 stream.  There is no eager fallback: tensors must live on a ROCm device.
 """
+import collections
 import math
 import ctypes as C
 import os
@@ -1993,11 +1994,74 @@ def _ban_operands(ban, rows, who):
     return _ptr(hist), hist.shape[1], int(t), int(n), -1 if eos is None else int(eos)
 
 
-def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None, row="auto"):
+# The decoding rules on the mixed distribution row (behind K32, before the argmax / top-W / draw): ``min_length`` zeroes row[eos] while
+# t < min_length, ``banned`` zeroes the listed ids at every step.  The limits of both, in one place: a list holds at most RULES_MAX_BANNED ids
+# per item; the rules need no history and have no step bound (NGRAM_MAX_T binds a pass only when the n-gram ban is on as well).
+RULES_MAX_BANNED = 256
+RowRules = collections.namedtuple("RowRules", "eos t min_length banned rows_per_item")
+RowRules.__doc__ = """What a head launch takes as ``rules=``: ``eos`` (the id ``min_length`` keeps out; -1: none), ``t`` (the 0-based step = the tokens
+a row has emitted), ``min_length`` (0 = off), ``banned`` (None, or a contiguous int32 [K] / [items, K] tensor on the rows' device, K <= 256; entries
+outside [0, V) are ignored) and ``rows_per_item`` (rows r of item r // rows_per_item share that item's list).  ``row_rules`` makes one per pass;
+``rules._replace(t=t)`` is the step's."""
+
+
+def decode_rules_supported():
+    return bool(A.lib.case_abi_features() & A.FEAT_DECODE_RULES)
+
+
+def row_rules(eos, min_length=0, banned=None, rows_per_item=1, t=0):
+    """The checked ``RowRules`` of a pass (made once, not per step): ``banned`` must already be an int32 tensor [K] or [items, K]."""
+    min_length, rows_per_item = int(min_length), int(rows_per_item)
+    if min_length < 0 or rows_per_item < 1:
+        raise ValueError("row_rules: min_length >= 0 and rows_per_item >= 1 (got %d, %d)" % (min_length, rows_per_item))
+    if banned is not None:
+        if not torch.is_tensor(banned) or banned.dtype != torch.int32 or banned.dim() not in (1, 2) or not banned.is_contiguous():
+            raise TypeError("row_rules: banned must be a contiguous int32 tensor [K] or [items, K]")
+        if banned.shape[-1] > RULES_MAX_BANNED:
+            raise ValueError("row_rules: at most %d banned ids per item (got %d)" % (RULES_MAX_BANNED, banned.shape[-1]))
+        if banned.numel() == 0:
+            banned = None
+    return RowRules(-1 if eos is None else int(eos), int(t), min_length, banned, rows_per_item)
+
+
+def _rule_operands(rules, rows, who):
+    """``rules`` (a ``RowRules``) -> (t, the trailing arguments of a ``_rules`` entry point: eos, min_length, banned, K, item stride, rows_per_item)."""
+    if not isinstance(rules, RowRules):
+        raise TypeError("%s: rules must be an ops.RowRules (ops.row_rules(...))" % who)
+    eos, t, min_length, banned, rpi = rules
+    if int(t) < 0 or int(min_length) < 0 or int(rpi) < 1:
+        raise ValueError("%s: t >= 0, min_length >= 0 and rows_per_item >= 1 (got %r, %r, %r)" % (who, t, min_length, rpi))
+    K = stride = 0
+    if banned is not None:
+        if banned.dtype != torch.int32 or banned.dim() not in (1, 2) or not banned.is_contiguous():
+            raise TypeError("%s: banned must be a contiguous int32 tensor [K] or [items, K]" % who)
+        K = banned.shape[-1]
+        if K > RULES_MAX_BANNED:
+            raise ValueError("%s: at most %d banned ids per item (got %d)" % (who, RULES_MAX_BANNED, K))
+        if banned.dim() == 2:
+            if rows % int(rpi) or banned.shape[0] * int(rpi) != rows:
+                raise ValueError("%s: %d rows, %d lists, rows_per_item %d" % (who, rows, banned.shape[0], rpi))
+            stride = K
+    return int(t), (int(eos), int(min_length), _ptr(banned) if K else None, K, stride, int(rpi))
+
+
+def _ban_operands_rules(ban, t, rows, who):
+    """The history operands of a ``_rules`` entry point at step ``t``: those of ``_ban_operands``, or no ban (NULL, 0, t, 0, -1)."""
+    if ban is None:
+        return (None, 0, t, 0, -1)
+    out = _ban_operands(ban, rows, who)
+    if out[2] != t:
+        raise ValueError("%s: the ban's step %d and the rules' step %d differ" % (who, out[2], t))
+    return out
+
+
+def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None, row="auto", rules=None):
     """logits f32 [B, V]; mix_logits f32 [B, 1 + nmem]; source_map a SortedSource over the concatenated memories; copies: list of f32
     [B, len_k] pointer weights -> (gen [B, V] | None, dist [B, V] | None, ids [B] int64) (no autograd: inference).
     ``ban`` = (hist int32 [B, Tmax], t, n, eos | None): K32, the n-gram ban before the argmax; the kernel appends ids at hist[:, t].
-    ``row``: "auto" | "lds" | "global" (``head_row_form``); both forms return the same bits wherever both run."""
+    ``row``: "auto" | "lds" | "global" (``head_row_form``); both forms return the same bits wherever both run.
+    ``rules`` (a ``RowRules``): min_length / banned ids zeroed behind the ban, before the argmax; with rules the ban is optional and, without
+    one, nothing is appended anywhere.  A row left all zero returns id 0."""
     B, V = logits.shape
     row = head_row_form(V, row, "pointer_head_decode")
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
@@ -2005,7 +2069,15 @@ def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, w
     dist = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_dist else None
     ids = torch.empty(B, dtype=torch.int64, device=logits.device)
     head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S)
-    if row == "global":
+    if rules is not None:
+        t, rule = _rule_operands(rules, B, "pointer_head_decode")
+        hist = _ban_operands_rules(ban, t, B, "pointer_head_decode")
+        if row == "global":
+            ws, stride = _row_workspace(B, V, logits.device)
+            A.call("case_pointer_head_decode_wide_rules", *head, _ptr(ws), stride, *hist, *rule, _stream())
+        else:
+            A.call("case_pointer_head_decode_rules", *head, *hist, *rule, _stream())
+    elif row == "global":
         ws, stride = _row_workspace(B, V, logits.device)
         A.call("case_pointer_head_decode_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, B, "pointer_head_decode"), _stream())
     elif ban is None:
@@ -2019,11 +2091,12 @@ def beam_supported(width):
     return 1 <= width <= 8 and bool(A.lib.case_abi_features() & A.FEAT_BEAM_DECODE)
 
 
-def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False, ban=None, row="auto"):
+def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=False, want_dist=False, ban=None, row="auto", rules=None):
     """K24, ``pointer_head_decode`` with a top-``width`` tail: -> (gen [R, V] | None, dist [R, V] | None, cand_p f32 [R, W], cand_id int64 [R, W]),
     the W largest entries of every row in descending order, the lowest id first among equals (no autograd: inference).  ``ban`` as in
     ``pointer_head_decode``, but the history is only read: row b * W + w is the hypothesis of slot w, which ``beam_advance`` maintains.
-    ``row`` as in ``pointer_head_decode``."""
+    ``row`` and ``rules`` as in ``pointer_head_decode`` (a zeroed entry can still be among the W candidates when fewer than W entries are
+    positive: its probability is 0.0, which ``beam_advance`` on a flat-history state treats as dead)."""
     R, V = logits.shape
     row = head_row_form(V, row, "pointer_head_topk")
     logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
@@ -2032,7 +2105,15 @@ def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=Fa
     cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
     cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
     head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, S, width)
-    if row == "global":
+    if rules is not None:
+        t, rule = _rule_operands(rules, R, "pointer_head_topk")
+        hist = _ban_operands_rules(ban, t, R, "pointer_head_topk")
+        if row == "global":
+            ws, stride = _row_workspace(R, V, logits.device)
+            A.call("case_pointer_head_beam_wide_rules", *head, _ptr(ws), stride, *hist, *rule, _stream())
+        else:
+            A.call("case_pointer_head_beam_rules", *head, *hist, *rule, _stream())
+    elif row == "global":
         ws, stride = _row_workspace(R, V, logits.device)
         A.call("case_pointer_head_beam_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, R, "pointer_head_topk"), _stream())
     elif ban is None:
@@ -2048,7 +2129,7 @@ def sample_supported(V):
 
 
 def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, t_last, eos, unk, pad, temperature, top_k, top_p, rng=None,
-                        uniforms=None, dist_in=None, want_gen=False, want_dist=False, ban=None, row="auto"):
+                        uniforms=None, dist_in=None, want_gen=False, want_dist=False, ban=None, row="auto", rules=None):
     """K28, ``pointer_head_decode`` with a draw instead of the argmax: -> (gen [R, V] | None, dist [R, V] | None, ids int64 [R], prob f32 [R]).
     One token per row is drawn from the mixed distribution after temperature, top-k and top-p (the rule: include/case_hip.h); ``ids`` is what
     the reference's ``sample`` loop emits for it (UNK for EOS at the first step, EOS at the last, PAD behind the end) and ``ended`` (uint8 [R])
@@ -2057,8 +2138,9 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     at counter ``rng_base + offset + r``.  ``dist_in`` f32 [R, V] with ``logits=None`` draws from a ready distribution instead of building the row
     (``mix_logits`` / ``source_map`` / ``copies`` unused).  ``ban`` = (hist int32 [R, Tmax], t, n): K32, the n-gram ban before pmax, the cuts and
     the draw (either row source; no ban for a row that has ended or whose history holds ``eos``); the kernel appends ``ids`` at hist[:, t].
-    ``row`` as in ``pointer_head_decode``; the wide form reads an aligned ``dist_in`` where it lies (V a multiple of 4, no ban).
-    No autograd (inference)."""
+    ``row`` as in ``pointer_head_decode``; the wide form reads an aligned ``dist_in`` where it lies (V a multiple of 4, no ban, no rules).
+    ``rules`` (a ``RowRules``; its ``eos`` is the rule's own, ``eos`` above stays the loop's): min_length / banned ids zeroed behind the ban, before
+    pmax, the cuts and the draw, for every row that has not ended.  No autograd (inference)."""
     if not (float(temperature) > 0.0) or int(top_k) < 0 or not (0.0 < float(top_p) <= 1.0):
         raise ValueError("pointer_head_sample: temperature must be > 0, top_k >= 0 and top_p in (0, 1]")
     if (logits is None) == (dist_in is None):
@@ -2086,7 +2168,15 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     tail = (_ptr(gen), _ptr(dist), _ptr(ids), _ptr(prob), _ptr(ended), _ptr(uniforms), R, V)
     draw = (float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), int(seed), int(offset), state, int(eos), int(unk), int(pad),
             int(bool(t_first)), int(bool(t_last)))
-    if row == "global":
+    if rules is not None:
+        t, rule = _rule_operands(rules, R, "pointer_head_sample")
+        hist = _ban_operands_rules(None if ban is None else tuple(ban) + (None,), t, R, "pointer_head_sample")[:4]
+        if row == "global":
+            ws, stride = _row_workspace(R, V, dev)
+            entry, draw = "case_pointer_head_sample_wide_rules", draw + (_ptr(ws), stride) + hist + rule + (_stream(),)
+        else:
+            entry, draw = "case_pointer_head_sample_rules", draw + hist + rule + (_stream(),)
+    elif row == "global":
         in_place = logits is None and ban is None and V % 4 == 0 and src.data_ptr() % 16 == 0
         ws, stride = (None, 0) if in_place else _row_workspace(R, V, dev)
         hist = (None, 0, 0, 0) if ban is None else _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4]
@@ -2163,6 +2253,20 @@ def ngram_ban_(dist, hist, t, n, eos=None, ended=None):
     return dist
 
 
+def row_rules_(dist, rules, ended=None):
+    """The decoding rules as a launch of their own (the unfused head), in place on dist f32 [R, V] (contiguous): row[eos] = 0.0 while
+    ``rules.t < rules.min_length`` and row[v] = 0.0 for every id v of the row's item's list; nothing else changes (no renormalisation).  A row
+    with ``ended`` (uint8 [R]) set is left alone.  -> dist."""
+    if dist.dtype != torch.float32 or dist.dim() != 2 or not dist.is_contiguous():
+        raise TypeError("row_rules_: dist must be a contiguous f32 [R, V]")
+    R, V = dist.shape
+    if ended is not None and (ended.dtype != torch.uint8 or tuple(ended.shape) != (R,) or not ended.is_contiguous()):
+        raise TypeError("row_rules_: ended must be a contiguous uint8 [R]")
+    t, rule = _rule_operands(rules, R, "row_rules_")
+    A.call("case_row_rules", _ptr(dist), _ptr(ended), R, V, t, *rule, _stream())
+    return dist
+
+
 def remove_duplicate_ids(out, len, n=3, pad=0):
     """K33: the reference's ``remove_duplicate`` on ``sentence_compact``'s outputs, in place: out int64 [B, T] front-packed ids, len int32 [B].
     Per row, while the length L > n: cut at the largest i in [1, L - n] whose tail out[i:L] holds only tokens of out[:i].  PAD behind the new
@@ -2207,9 +2311,16 @@ class BeamState(object):
         return self.flat[t % 2].view(self.B * self.W, self.T)
 
 
-def beam_advance(state, cand_p, cand_id, t, eos):
+def beam_advance(state, cand_p, cand_id, t, eos, length_penalty=1.0):
     """K25: step ``t`` of the search on ``state`` (in place) from the candidates cand_p f32 / cand_id int64 [B * W, W] of the step's rows.  A state
-    with the flat history gets it advanced in the same launch (and there a candidate of probability 0, a banned entry, is dead)."""
+    with the flat history gets it advanced in the same launch (and there a candidate of probability 0, a banned entry, is dead).
+    ``length_penalty`` = alpha >= 0: the key of a candidate and of a retiring hypothesis is cost / (len + 1)^alpha; 1.0 is the reference's
+    cost / (len + 1), the same launch as without the argument; any other value needs a flat-history state."""
+    alpha = float(length_penalty)
+    if not (alpha >= 0.0) or alpha == float("inf"):
+        raise ValueError("beam_advance: length_penalty must be a finite float >= 0, not %r" % (length_penalty,))
+    if alpha != 1.0 and state.flat is None:
+        raise ValueError("beam_advance: a length_penalty other than 1.0 needs a BeamState with the flat history (flat=True)")
     B, W = state.B, state.W
     if tuple(cand_p.shape) != (B * W, W) or tuple(cand_id.shape) != (B * W, W) or cand_p.dtype != torch.float32 or cand_id.dtype != torch.int64:
         raise TypeError("beam_advance: candidates must be f32 / int64 [B * W, W]")
@@ -2220,6 +2331,8 @@ def beam_advance(state, cand_p, cand_id, t, eos):
             -1 if eos is None else eos)
     if state.flat is None:
         A.call("case_beam_advance", *args, _stream())
+    elif alpha != 1.0:
+        A.call("case_beam_advance_rules", *args, _ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T, alpha, _stream())
     else:
         A.call("case_beam_advance_ban", *args, _ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T, _stream())
 

@@ -78,7 +78,8 @@ enum {
   CASE_FEAT_NGRAM_BAN = 1u << 22,         /* K32 / K33 case_ngram_ban, the `_ban` forms of K23 / K24 / K25 / K28, case_remove_duplicate_ids */
   CASE_FEAT_NGRAM_COUNTS = 1u << 23,      /* K34 / K35 case_ngram_counts / case_bleu_scores */
   CASE_FEAT_RANK_METRICS = 1u << 24,      /* K36 case_rank_metrics */
-  CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25  /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
+  CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25, /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
+  CASE_FEAT_DECODE_RULES = 1u << 26       /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -575,6 +576,66 @@ int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id, uint8_t* 
                           int64_t B, int32_t W, int64_t eos, const int32_t* flat_old, int32_t* flat_new, int64_t Tmax, case_stream_t stream);
 int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
                    case_stream_t stream);
+/* The decoding rules (CASE_FEAT_DECODE_RULES; purely additive, generation 600 unchanged): min_length, banned ids and the beam length penalty.
+ * The row rules act on the mixed distribution row of step t (t = the 0-based step = the tokens the row has emitted, BOS excluded), AFTER K32 and
+ * BEFORE the selection (argmax, top-W, pmax / cuts / draw), with plain stores of 0.0 and no renormalisation -- K32's contract, so top / cand_p /
+ * prob stay the model's own probabilities and a returned dist is the row after the ban and the rules:
+ *   min_length: row[eos] = 0.0 while t < min_length (min_length >= 0, 0 = off; eos outside [0, V), e.g. -1: no effect);
+ *   banned:     row[v] = 0.0 at every step for every v in the row's item's list.  banned int32 [K] with banned_stride = 0 (one list for every
+ *               row) or [R / rows_per_item, K] with banned_stride = K (row r takes list r / rows_per_item; R a multiple of rows_per_item >= 1).
+ *               0 <= K <= 256 (K = 0: off, banned may be NULL); entries outside [0, V) are ignored (-1 pads a ragged list); duplicates are legal.
+ * Limits, all of them: K <= 256 (CASE_E_UNSUPPORTED beyond).  The rules need no history and have NO step bound; K32's t <= 256 binds a call
+ * only when it also asks for the n-gram ban.  The rules apply to every row at every step, whatever its history holds; the one exception is a K28
+ * row with ended[r] != 0, which is left alone (it emits PAD with probability 1).  A row whose every entry ends up 0.0 behaves as an all-zero row
+ * does: id 0, value 0.
+ * Each `_rules` head takes the arguments of its `_ban` / `_wide` sibling, with the ban OPTIONAL (hist == NULL or n == 0: no ban, nothing is
+ * appended, Tmax is not read; otherwise K32 exactly as above, appends included), then the rule operands: eos, min_length, banned, K,
+ * banned_stride, rows_per_item.  `ban_eos` is K32's eos (its "history holds eos" clause); K28's own eos plays that part in the sample forms,
+ * whose rule eos is `rule_eos`.  With min_length = 0 and K = 0 a `_rules` head returns the bits of its sibling.  The wide `_rules` forms always
+ * need row_ws (dist_in is never read in place).
+ * case_row_rules: the same rules on dist f32 [R, V] in place (one wave per row; ended u8 [R] nullable: rows with ended != 0 are left alone).
+ * case_beam_advance_rules: case_beam_advance_ban (flat history; a candidate of probability exactly 0 is dead, so a zeroed entry never enters a
+ *   hypothesis even when fewer than W entries survive) with the key cost / (len + 1)^length_penalty for candidates and retiring hypotheses
+ *   (powf in f32; cost = cum - log(p + 1e-10), len counts BOS), so fin_key / beam_scores are these keys.  length_penalty finite and >= 0;
+ *   exactly 1.0 is case_beam_advance_ban's own launch (the division, bit for bit). */
+int case_pointer_head_decode_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                   const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                   int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length,
+                                   const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item, case_stream_t stream);
+int case_pointer_head_beam_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies, const int64_t* lens,
+                                 int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W,
+                                 const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length,
+                                 const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item, case_stream_t stream);
+int case_pointer_head_sample_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                   const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                   uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                   float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad,
+                                   int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t rule_eos,
+                                   int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item,
+                                   case_stream_t stream);
+int case_pointer_head_decode_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                        int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
+                                        int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
+                                        int64_t rows_per_item, case_stream_t stream);
+int case_pointer_head_beam_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                      int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
+                                      int64_t t, int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
+                                      int64_t banned_stride, int64_t rows_per_item, case_stream_t stream);
+int case_pointer_head_sample_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
+                                        int64_t pad, int32_t first, int32_t last, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax,
+                                        int64_t t, int32_t n, int64_t rule_eos, int32_t min_length, const int32_t* banned, int32_t K,
+                                        int64_t banned_stride, int64_t rows_per_item, case_stream_t stream);
+int case_row_rules(float* dist, const uint8_t* ended, int64_t R, int64_t V, int64_t t, int64_t eos, int32_t min_length, const int32_t* banned,
+                   int32_t K, int64_t banned_stride, int64_t rows_per_item, case_stream_t stream);
+int case_beam_advance_rules(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent, int64_t* token,
+                            int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step, int32_t* fin_slot, int64_t t, int64_t T,
+                            int64_t B, int32_t W, int64_t eos, const int32_t* flat_old, int32_t* flat_new, int64_t Tmax, float length_penalty,
+                            case_stream_t stream);
 /* The wide forms of K23 / K24 / K28 (CASE_FEAT_POINTER_HEAD_WIDE; purely additive, generation 600 unchanged): the same kernels with the
  * vocabulary row of a workgroup in device memory instead of LDS, for vocabularies beyond 36000 ids.  Each takes the arguments of its LDS
  * sibling, then row_ws, row_stride, then the history operands of the `_ban` form (hist == NULL or n == 0: no ban; otherwise K32 exactly as above).
