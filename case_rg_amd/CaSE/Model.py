@@ -12,7 +12,7 @@ from .. import config, ops
 from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, decode_rules_param, no_repeat_ngram_param, sampling_params
-from ..common.Utils import to_sentence
+from ..common.Utils import to_sentence, token_freq_table
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
 from ..evaluation.rouge_ids import consensus_answers
 
@@ -131,6 +131,13 @@ class ResponseGeneration(nn.Module):
         self.UNK = UNK
         self.decoder = decoder
 
+    @staticmethod
+    def token_prior(passage_score, token_score):
+        """sigma(passage) * sigma(token), normalised over all P*Lp tokens of an item (:239-241): [B, P*Lp] f32 scalars (glue).  The decoder
+        weighs its copy attention by it, and ``CaSE.do_extract`` returns it."""
+        prior = (torch.sigmoid(passage_score).unsqueeze(-1) * torch.sigmoid(token_score)).reshape(token_score.size(0), -1)
+        return prior / (1e-8 + prior.sum(dim=-1, keepdim=True))
+
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
                span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0,
                decode_rules=None):
@@ -138,9 +145,7 @@ class ResponseGeneration(nn.Module):
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
         H = passage_rep[0].size(-1)
-        # sigma(passage) * sigma(token), normalised over all P*Lp tokens (:239-241): [B, P*Lp] f32 scalars (glue)
-        prior = (torch.sigmoid(passage_score).unsqueeze(-1) * torch.sigmoid(token_score)).reshape(B, -1)
-        prior = prior / (1e-8 + prior.sum(dim=-1, keepdim=True))
+        prior = self.token_prior(passage_score, token_score)
         mem = passage_rep[0].reshape(B, -1, H)
         answer_rep = ops.bmm(ops.cast_to(prior.unsqueeze(1), mem.dtype), mem, b_is_kn=True).squeeze(1)  # prior @ reps (:242)
         prior_p = prior.reshape_as(token_score)
@@ -183,6 +188,9 @@ class CaSE(nn.Module):
         self.min_length = 0
         self.banned_ids = None
         self.length_penalty = 1.0
+        self.support_top_k = 32  # do_extract's default K: this many supporting tokens per item
+        # the per-id frequency table of the token supervision (K37), installed by set_token_freq: it moves with .to() and is no state_dict key
+        self.register_buffer("token_freq", None, persistent=False)
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -203,12 +211,45 @@ class CaSE(nn.Module):
                                          passage_selection_result=ps)
         return eq, ep, ps, se
 
+    def set_token_freq(self, vocab_freq):
+        """Install the per-id frequency table of the token supervision: a 1-D tensor of counts (the count of id v at [v]) or the reference's
+        ``{id: count}`` dict; None removes it.  With it ``do_train`` and ``evaluate_extract`` label a batch that carries no ``token_label`` /
+        ``token_weight`` on the device (K37)."""
+        self.token_freq = None if vocab_freq is None else token_freq_table(vocab_freq, next(self.parameters()).device)
+        return self
+
+    def _token_labels(self, data, response=None, who="label_batch"):
+        if self.token_freq is None:
+            raise ValueError("%s: data carries no token_label / token_weight and no frequency table is installed to compute them from: "
+                             "call set_token_freq(vocab_freq) first" % who)
+        return ops.token_labels(data['passage'], data['response'] if response is None else response, self.token_freq)
+
+    def label_batch(self, data, response=None):
+        """A shallow copy of ``data`` with ``token_label`` and ``token_weight`` f32 [B, P, L] computed on the device (K37, ``common.Utils.
+        token_label``'s rule) from ``data['passage']``, the table of ``set_token_freq`` and ``response`` int64 [B, T] (default
+        ``data['response']``).  Any answer may be given -- a ``do_consensus`` pick, a rescored sample --: its non-PAD ids are the answer set
+        as they stand, so the caller strips BOS / EOS where they should not count."""
+        out = dict(data)
+        out['token_label'], out['token_weight'] = self._token_labels(data, response)
+        return out
+
+    def _token_supervision(self, data):
+        """(token_label, token_weight) of a training batch: the two entries of ``data``, or K37's where ``data`` carries neither."""
+        has_label, has_weight = 'token_label' in data, 'token_weight' in data
+        if has_label != has_weight:
+            raise ValueError("do_train: data carries %s without %s: give both, or neither (they are then computed on the device, set_token_freq)" % (
+                ("token_label", "token_weight") if has_label else ("token_weight", "token_label")))
+        if has_label:
+            return data['token_label'], data['token_weight']
+        return self._token_labels(data, who="do_train")
+
     def do_train(self, data):
+        token_label, token_weight = self._token_supervision(data)
         eq, ep, ps, se = self._encode_select_extract(data)
         loss_ps = passage_bce(ps[0], data['passage_label'])
         valid = data['passage'].ne(0).float()
-        bce = torch.nn.functional.binary_cross_entropy_with_logits(se[0], data['token_label'].detach(), reduction='none')
-        loss_se = (valid * bce * data['token_weight'].detach()).sum() / valid.sum()
+        bce = torch.nn.functional.binary_cross_entropy_with_logits(se[0], token_label.detach(), reduction='none')
+        loss_se = (valid * bce * token_weight.detach()).sum() / valid.sum()
         rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
                                              output=data['response'])
@@ -320,6 +361,39 @@ class CaSE(nn.Module):
             raise ValueError("do_rank runs in eval mode: call model.eval() first")
         return {'rank': self._encode_select(data)[2][0]}
 
+    def do_extract(self, data, top_k=None, select="prior", labels=None):
+        """The supporting tokens alone (eval mode only): the encoders, the selection stage and the token-identification stage run, the
+        decoder does not -> ``rank`` [B, P] (the bits of ``do_rank``); ``token_score`` f32 [B, P, L] (the stage's logits, -1e6 at PAD);
+        ``token_prior`` f32 [B, P, L] (sigmoid(rank) x sigmoid(token_score) normalised over the item's P L tokens: the weights of the
+        decoder's copy attention); and the K best non-PAD tokens of every item, best first (K38: key descending, then the lower position):
+        ``support_pos`` int32 [B, K] (flat positions p L + l, -1 behind the item's non-PAD tokens), ``support_ids`` int64 [B, K] (``passage``
+        there, PAD where the position is -1), ``support_value`` f32 [B, K] (the key there, 0 where the position is -1).  K = ``top_k``
+        (None: ``self.support_top_k``), at most 256; P L <= 16384.  ``select="prior"`` ranks by ``token_prior``, ``"score"`` by
+        ``token_score`` alone.  ``labels`` f32 [B, P, L] (e.g. ``token_label``): the same launch also counts, per item, ``counts`` int32
+        [B, 5] = n_valid, n_pos, n_pred (token_score > 0), tp, hits (``ops.TOKEN_COUNTS``).  Nothing is read back."""
+        if self.training:
+            raise ValueError("do_extract runs in eval mode: call model.eval() first")
+        if select not in ("prior", "score"):
+            raise ValueError("do_extract: select must be 'prior' or 'score', not %r" % (select,))
+        K = int(self.support_top_k if top_k is None else top_k)
+        B, P, L = data['passage'].shape
+        if not 1 <= K <= ops.TOKEN_MAX_K or P * L > ops.TOKEN_MAX_L:
+            raise ValueError("do_extract: 1 .. %d supporting tokens out of up to %d (got top_k %d, P x L = %d)" % (
+                ops.TOKEN_MAX_K, ops.TOKEN_MAX_L, K, P * L))
+        _, _, ps, se = self._encode_select_extract(data)
+        token_score = se[0]
+        prior = self.response_generation.token_prior(ps[0], token_score)
+        flat_score = token_score.reshape(B, -1)
+        picked = ops.token_select(prior if select == "prior" else flat_score, data['passage'].ne(0).reshape(B, -1), K,
+                                  scores=None if labels is None else flat_score, labels=None if labels is None else labels.reshape(B, -1).float())
+        pos = picked['pos']
+        ids = data['passage'].reshape(B, -1).gather(1, pos.clamp(min=0).long()).masked_fill(pos < 0, 0)
+        out = {'rank': ps[0], 'token_score': token_score, 'token_prior': prior.reshape_as(token_score), 'support_pos': pos,
+               'support_ids': ids, 'support_value': picked['value']}
+        if labels is not None:
+            out['counts'] = picked['counts']
+        return out
+
     def forward(self, data, method='mle_train'):
         # the reference expands data['source_map'] into a dense one-hot here (Utils.build_map, 15 GB at cfg 2);
         # the ids themselves feed the pointer scatter kernel instead
@@ -337,3 +411,5 @@ class CaSE(nn.Module):
             return self.do_consensus(data)
         elif method == 'rank':
             return self.do_rank(data)
+        elif method == 'extract':
+            return self.do_extract(data)

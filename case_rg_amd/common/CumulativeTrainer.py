@@ -353,3 +353,36 @@ class CumulativeTrainer(object):
             return dict({name: float('nan') for name in ops.RANK_METRICS}, items=0)
         sums = total.tolist()  # (the one read-back of the evaluation)
         return dict({name: s / items for name, s in zip(ops.RANK_METRICS, sums)}, items=items)
+
+    def evaluate_extract(self, dataset, collate_fn, batch_size, top_k=None, select="prior", labels="token_label"):
+        """Token-level metrics of the supporting-token stage: ``model.do_extract(data, top_k, select, labels=data[labels])`` per batch (K38
+        counts the items while it selects their tokens), the column sums kept on the device, one read-back at the end -> dict(precision =
+        tp / n_pred and recall = tp / n_pos of the tokens whose logit is positive, f1 = their harmonic mean, precision_at_k = hits /
+        sum of min(K, n_valid) and recall_at_k = hits / n_pos of the K tokens ``select`` ranks first, items, tokens = the non-PAD tokens
+        counted); micro-averages over tokens, 0.0 where a denominator is 0.  Where ``data`` lacks ``labels`` they come from
+        ``model.label_batch(data)`` (K37; ``set_token_freq`` first).  One process, under no_grad in eval mode; the model's mode is restored
+        afterwards."""
+        was_training = self.model.training
+        self.model.eval()
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    gold = data[labels] if labels in data else self.model.label_batch(data)['token_label']
+                    counts = self.model.do_extract(data, top_k=top_k, select=select, labels=gold)['counts'].long()
+                    K = self.model.support_top_k if top_k is None else int(top_k)
+                    part = torch.cat([counts.sum(0), counts[:, 0].clamp(max=K).sum().reshape(1)])
+                    total = part if total is None else total + part
+                    items += counts.shape[0]
+        finally:
+            self.model.train(was_training)
+        names = ("precision", "recall", "f1", "precision_at_k", "recall_at_k")
+        if items == 0:
+            return dict({name: float('nan') for name in names}, items=0, tokens=0)
+        n_valid, n_pos, n_pred, tp, hits, slots = total.tolist()  # (the one read-back of the evaluation)
+        ratio = lambda a, b: a / b if b else 0.0  # noqa: E731
+        precision, recall = ratio(tp, n_pred), ratio(tp, n_pos)
+        return dict(precision=precision, recall=recall, f1=ratio(2 * precision * recall, precision + recall),
+                    precision_at_k=ratio(hits, slots), recall_at_k=ratio(hits, n_pos), items=items, tokens=n_valid)

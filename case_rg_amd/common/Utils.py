@@ -149,6 +149,77 @@ def remove_duplicate_ids(ids, len, n=3, pad=0):
     return ops.remove_duplicate_ids(ids, len, n, pad)
 
 
+def token_freq_table(vocab_freq, device=None):
+    """``vocab_freq`` as the 1-D table K37 reads (the count of id v at [v]): a ``{id: count}`` dict becomes an int64 table (f32 when a
+    count is not an integer) as long as its largest id + 1; a 1-D tensor is taken as it is (integer -> int64, floating -> f32)."""
+    if isinstance(vocab_freq, dict):
+        size = max((int(i) for i in vocab_freq), default=-1) + 1
+        whole = all(float(c) == int(c) for c in vocab_freq.values())
+        table = torch.zeros(size, dtype=torch.int64 if whole else torch.float32)
+        if size:
+            ids = torch.tensor([int(i) for i in vocab_freq], dtype=torch.int64)
+            table[ids] = torch.tensor([c for c in vocab_freq.values()], dtype=table.dtype)
+    elif torch.is_tensor(vocab_freq) and vocab_freq.dim() == 1:
+        table = vocab_freq.detach().to(torch.float32 if vocab_freq.is_floating_point() else torch.int64)
+    else:
+        raise TypeError("vocab_freq must be a 1-D tensor of counts or an {id: count} dict")
+    return table if device is None else table.to(device)
+
+
+def token_label(passage, response, vocab_freq, pad=0):
+    """The supervision of the supporting-token stage (reference: CaSE/CaSEDataset.py ``token_label``, a Python loop over every token) as
+    vectorised torch on the device of ``passage``: passage int64 [B, P, L] with response int64 [B, T], or [P, L] with [T]; ``vocab_freq`` a
+    1-D tensor of counts or an ``{id: count}`` dict (0 for an id without an entry) -> (label, weight) f32 of ``passage``'s shape.  With
+    A = the ids of the response other than ``pad``, for every row x[0..L):
+        label[i] = g1[i] = 1 where x[i] is in A (``pad`` never is)
+        g3[i], g5[i] = the number of DISTINCT ids in A among x[i-1 .. i+1] and x[i-2 .. i+2] (positions outside the row read ``pad``)
+        lf[i] = ln(f[x[i]] + 2),  S = the sum of lf over all L positions (PAD positions included, as in the reference)
+        weight[i] = (S / lf[i] * g1[i] * g3[i] * g5[i]) ^ 0.2 where g1[i] = 1, exactly 1 elsewhere
+    All arithmetic is f64, rounded to f32 once.  K37 (``ops.token_labels``) is the same rule in one launch."""
+    label, weight = token_label_f64(passage, response, vocab_freq, pad)
+    return label.float(), weight.float()
+
+
+def token_label_f64(passage, response, vocab_freq, pad=0):
+    """``token_label`` before its one rounding: (label, weight) as f64."""
+    if passage.dim() == 2 and response.dim() == 1:
+        label, weight = token_label_f64(passage.unsqueeze(0), response.unsqueeze(0), vocab_freq, pad)
+        return label[0], weight[0]
+    if passage.dim() != 3 or response.dim() != 2 or response.shape[0] != passage.shape[0]:
+        raise TypeError("token_label: passage [B, P, L] with response [B, T], or [P, L] with [T]")
+    B, P, L = passage.shape
+    x, y = passage.long(), response.long().to(passage.device)
+    if torch.is_tensor(vocab_freq) and vocab_freq.dim() == 1:
+        table = vocab_freq.detach().to(x.device).double()
+    else:
+        table = token_freq_table(vocab_freq, x.device).double()
+    member = ((x.unsqueeze(-1) == y[:, None, None, :]) & y.ne(pad)[:, None, None, :]).any(-1) & x.ne(pad)
+    # the five slots of every window, the row extended by two PAD positions on either side
+    xp = torch.nn.functional.pad(x, (2, 2), value=pad)
+    mp = torch.nn.functional.pad(member, (2, 2), value=False)
+    ids, flags = [xp[..., j:j + L] for j in range(5)], [mp[..., j:j + L] for j in range(5)]
+
+    def distinct(first, last):  # members of slots first..last that no earlier slot of the window repeats
+        count = torch.zeros_like(x)
+        for j in range(first, last + 1):
+            new = flags[j].clone()
+            for k in range(first, j):
+                new &= ids[k].ne(ids[j])
+            count += new
+        return count
+
+    g3, g5 = distinct(1, 3), distinct(0, 4)
+    F = table.numel()
+    inside = (x >= 0) & (x < F)
+    f = torch.where(inside, table[x.clamp(0, max(F - 1, 0))], torch.zeros((), dtype=torch.float64, device=x.device)) if F else \
+        torch.zeros(x.shape, dtype=torch.float64, device=x.device)
+    lf = torch.log(f + 2.0)
+    g1 = member.double()
+    weight = (lf.sum(-1, keepdim=True) / lf * g1 * g3.double() * g5.double()).pow(0.2)
+    weight = torch.where(member, weight, torch.ones((), dtype=torch.float64, device=x.device))
+    return g1, weight
+
+
 def banned_tokens(history, n, vocab_size=None, eos=None):
     """The n-gram ban (K32) restated on a Python list: ``history`` = the ids a row has emitted so far (BOS excluded), t = len(history).
     -> the sorted ids v such that some j <= t - n has history[j : j + n - 1] == history[t - n + 1 : t] and history[j + n - 1] == v; for

@@ -2636,3 +2636,74 @@ def rank_metrics(scores, rel, keys=None, valid=None, extra_rel=None):
     A.call("case_rank_metrics", _ptr(scores), _ptr(keys), _ptr(rel), _ptr(_u8(valid)), _ptr(extra_rel), _ptr(order), _ptr(metrics),
            _ptr(num_rel), B, P, R, _stream())
     return dict(order=order, metrics=metrics, num_rel=num_rel)
+
+
+# K37 / K38: the supporting-token stage's supervision and its best tokens
+TOKEN_MAX_L, TOKEN_MAX_T, TOKEN_MAX_K = 16384, 1024, 256
+TOKEN_COUNTS = ("n_valid", "n_pos", "n_pred", "tp", "hits")  # the columns of ``counts``
+
+
+def token_labels_supported():
+    return bool(A.lib.case_abi_features() & A.FEAT_TOKEN_LABELS)
+
+
+def token_labels(passage, response, freq, pad=0):
+    """K37: passage int64 [B, P, L], response int64 [B, T] (``pad`` where there is no token), freq f32 or int64 [F] (the count of id v at
+    freq[v]; 0 for v >= F) -> (label, weight) f32 [B, P, L]: ``common.Utils.token_label``'s rule (the reference's CaSEDataset.py
+    token_label), f64 inside and rounded once.  L <= 16384, T <= 1024, ids in [0, 2^31) (not checked: compared on 32 bits)."""
+    if passage.dtype != torch.int64 or passage.dim() != 3:
+        raise TypeError("token_labels: passage must be int64 [B, P, L]")
+    B, P, L = passage.shape
+    if response.dtype != torch.int64 or response.dim() != 2 or response.shape[0] != B:
+        raise TypeError("token_labels: response must be int64 [B, T] for passage [%d, %d, %d]" % (B, P, L))
+    if freq.dtype not in (torch.float32, torch.int64) or freq.dim() != 1:
+        raise TypeError("token_labels: freq must be f32 or int64 [F]")
+    T = response.shape[1]
+    if B < 1 or P < 1 or L < 1 or T < 1:
+        raise ValueError("token_labels: at least one item, passage, token and answer slot (got passage %s, response %s)" % (
+            tuple(passage.shape), tuple(response.shape)))
+    if L > TOKEN_MAX_L or T > TOKEN_MAX_T:
+        raise ValueError("token_labels: rows of up to %d tokens and answers of up to %d ids (got %d and %d)" % (TOKEN_MAX_L, TOKEN_MAX_T, L, T))
+    if not token_labels_supported():
+        raise RuntimeError("token_labels: this build of the library lacks K37 / K38 (CASE_FEAT_TOKEN_LABELS)")
+    passage, response, freq = (t if t.is_contiguous() else t.contiguous() for t in (passage, response, freq))
+    label = torch.empty(B, P, L, dtype=torch.float32, device=passage.device)
+    weight = torch.empty(B, P, L, dtype=torch.float32, device=passage.device)
+    A.call("case_token_labels", _ptr(passage), _ptr(response), _ptr(freq) if freq.numel() else None, int(freq.dtype == torch.int64),
+           _ptr(label), _ptr(weight), B, P, L, T, freq.numel(), int(pad), _stream())
+    return label, weight
+
+
+def token_select(values, valid, k, scores=None, labels=None):
+    """K38: values f32 [B, S] (one item per row), valid bool [B, S] -> dict(pos int32 [B, k]: the positions of the k best valid keys, best
+    first -- value descending, NaN as -inf, -0.0 == +0.0, then the LOWER position --, -1 behind the valid ones; value f32 [B, k]: ``values``
+    there, 0 where pos is -1).  With ``labels`` f32 [B, S] also counts int32 [B, 5] in ``TOKEN_COUNTS``' order: n_valid, n_pos (valid and
+    label > 0.5), n_pred (valid and score > 0; ``scores`` f32 [B, S], default ``values``), tp (both), hits (label > 0.5 among the selected).
+    S <= 16384, k <= 256."""
+    if values.dtype != torch.float32 or values.dim() != 2:
+        raise TypeError("token_select: values must be f32 [B, S]")
+    B, S = values.shape
+    if valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, S):
+        raise TypeError("token_select: valid must be bool [B, S]")
+    for name, t in (("scores", scores), ("labels", labels)):
+        if t is not None and (t.dtype != torch.float32 or tuple(t.shape) != (B, S)):
+            raise TypeError("token_select: %s must be f32 [B, S]" % name)
+    if scores is not None and labels is None:
+        raise TypeError("token_select: scores are read for the counts only, which need labels")
+    k = int(k)
+    if B < 1 or S < 1 or k < 1:
+        raise ValueError("token_select: at least one item, one position and k = 1 (got [%d, %d], k %d)" % (B, S, k))
+    if S > TOKEN_MAX_L or k > TOKEN_MAX_K:
+        raise ValueError("token_select: rows of up to %d keys and up to %d selected positions (got %d and %d)" % (TOKEN_MAX_L, TOKEN_MAX_K, S, k))
+    if not token_labels_supported():
+        raise RuntimeError("token_select: this build of the library lacks K37 / K38 (CASE_FEAT_TOKEN_LABELS)")
+    values = values if values.is_contiguous() else values.contiguous()
+    scores, labels = (None if t is None else t.contiguous() for t in (scores, labels))
+    pos = torch.empty(B, k, dtype=torch.int32, device=values.device)
+    val = torch.empty(B, k, dtype=torch.float32, device=values.device)
+    counts = None if labels is None else torch.empty(B, len(TOKEN_COUNTS), dtype=torch.int32, device=values.device)
+    A.call("case_token_select", _ptr(values), _ptr(_u8(valid)), _ptr(scores), _ptr(labels), _ptr(pos), _ptr(val), _ptr(counts), B, S, k, _stream())
+    out = dict(pos=pos, value=val)
+    if counts is not None:
+        out["counts"] = counts
+    return out

@@ -79,7 +79,8 @@ enum {
   CASE_FEAT_NGRAM_COUNTS = 1u << 23,      /* K34 / K35 case_ngram_counts / case_bleu_scores */
   CASE_FEAT_RANK_METRICS = 1u << 24,      /* K36 case_rank_metrics */
   CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25, /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
-  CASE_FEAT_DECODE_RULES = 1u << 26       /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
+  CASE_FEAT_DECODE_RULES = 1u << 26,      /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
+  CASE_FEAT_TOKEN_LABELS = 1u << 27       /* K37 / K38 case_token_labels / case_token_select */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -852,6 +853,30 @@ int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t
  * ------------------------------------------------------------------------------------------- */
 int case_rank_metrics(const float* scores, const int32_t* keys, const int32_t* rel, const uint8_t* valid, const int32_t* extra_rel,
                       int32_t* order, double* metrics, int32_t* num_rel, int64_t B, int64_t P, int64_t R, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * The supporting-token stage (CASE_FEAT_TOKEN_LABELS; purely additive, generation 600 unchanged): its supervision and its best tokens.
+ * K37 case_token_labels: the reference's CaSEDataset.py token_label on tensors (common/Utils.py token_label states the rule).  For every row
+ *   x[0..L) of passage int64 [B, P, L], with A = the ids of response int64 [b, 0..T) other than `pad` and f = freq ([F], f32, or int64 with
+ *   freq_is_i64 != 0; f[v] = 0 for v >= F):
+ *     label[i]  = g1[i] = 1 where x[i] is in A (pad never is), else 0
+ *     g3[i], g5[i] = the number of DISTINCT ids in A among x[i-1 .. i+1] and x[i-2 .. i+2] (positions outside the row read pad)
+ *     lf[i] = ln(f[x[i]] + 2),  S = the sum of lf over all L positions (PAD positions included)
+ *     weight[i] = (S / lf[i] * g3[i] * g5[i]) ^ 0.2 where g1[i] = 1, exactly 1 elsewhere
+ *   label, weight f32 [B, P, L].  ln, the sum (a tree of fixed shape) and the power are f64, the result is rounded once: two launches give
+ *   the same bits.  Ids must lie in [0, 2^31); L <= 16384 and T <= 1024, or CASE_E_UNSUPPORTED.
+ * K38 case_token_select: every row of values f32 [B, S] is one item; valid u8 [B, S] (NULL: all) says which positions hold a token.
+ *     pos[b, r] int32: the position at rank r (0-based) in the order: value descending (K36's map: -0.0 == +0.0, NaN as -inf), then the
+ *                      LOWER position; an invalid position is never selected; -1 behind the valid ones.    val[b, r] f32: values at pos, 0 there
+ *   With labels f32 [B, S] (then counts must be given, else both NULL) counts int32 [B, 5] = n_valid, n_pos (valid and label > 0.5), n_pred
+ *   (valid and score > 0; scores f32 [B, S], NULL: values), tp (both), hits (label > 0.5 among the selected).
+ *   S <= 16384 and K <= 256, or CASE_E_UNSUPPORTED.
+ * Both are asynchronous on `stream`, use no atomics and write every output element.
+ * ------------------------------------------------------------------------------------------- */
+int case_token_labels(const int64_t* passage, const int64_t* response, const void* freq, int32_t freq_is_i64, float* label, float* weight,
+                      int64_t B, int64_t P, int64_t L, int64_t T, int64_t F, int64_t pad, case_stream_t stream);
+int case_token_select(const float* values, const uint8_t* valid, const float* scores, const float* labels, int32_t* pos, float* val,
+                      int32_t* counts, int64_t B, int64_t S, int32_t K, case_stream_t stream);
 
 #ifdef __cplusplus
 }
