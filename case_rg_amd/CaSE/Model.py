@@ -14,6 +14,7 @@ from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, decode_rules_param, no_repeat_ngram_param, sampling_params
 from ..common.Utils import to_sentence, token_freq_table
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
+from ..evaluation.attribution import attribute_answers
 from ..evaluation.rouge_ids import consensus_answers
 
 
@@ -53,10 +54,10 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
-                score_index=None, no_repeat_ngram=0, decode_rules=None):
+                score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
                          score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram,
-                         decode_rules=decode_rules)
+                         decode_rules=decode_rules, segments=segments)
 
 
 class RelevantPassageSelection(nn.Module):
@@ -140,7 +141,7 @@ class ResponseGeneration(nn.Module):
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
                span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0,
-               decode_rules=None):
+               decode_rules=None, segments=None):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -154,7 +155,7 @@ class ResponseGeneration(nn.Module):
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)
 
 
 class CaSE(nn.Module):
@@ -256,9 +257,9 @@ class CaSE(nn.Module):
         dist1, dist2 = rg[2]
         return [loss_ps, loss_se, generation_nll(ops.add(dist1, dist2), data['response'])]
 
-    def _respond(self, data, **mode):
+    def _respond(self, data, _enc=None, **mode):
         """Encode, select, extract, then the decoder in the mode the keyword names: (the decoder's raw result, rank)."""
-        eq, ep, ps, se = self._encode_select_extract(data)
+        eq, ep, ps, se = self._encode_select_extract(data) if _enc is None else _enc  # (do_attribute encodes once for two passes)
         rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
                                              output=None, **mode)
@@ -274,29 +275,29 @@ class CaSE(nn.Module):
                                   self.length_penalty if length_penalty is None else length_penalty, self.vocab2id, data['query'].size(0),
                                   self.max_target_length, device=data['query'].device)
 
-    def do_test(self, data, no_repeat_ngram=None, min_length=None, banned_ids=None):
+    def do_test(self, data, no_repeat_ngram=None, min_length=None, banned_ids=None, _enc=None):
         """Greedy decoding.  ``no_repeat_ngram`` (None = ``self.no_repeat_ngram``; 0 = off): at every step the tokens that would complete an
         n-gram the answer already holds get probability 0 before the argmax (K32); max_target_length <= 256 with it on.  ``min_length`` /
         ``banned_ids`` (None = the model's attributes): no EOS among the first ``min_length`` tokens, and the listed ids ([K], or [B, K] per item)
         are never emitted -- their entries of the distribution are zeroed before the argmax, nothing is renormalised."""
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, no_repeat_ngram=self._ngram(no_repeat_ngram),
+        rg, rank = self._respond(data, _enc=_enc, max_target_length=self.max_target_length, no_repeat_ngram=self._ngram(no_repeat_ngram),
                                  decode_rules=self._rules(data, min_length, banned_ids))
         return {'answer': rg[3], 'rank': rank}
 
     do_infer = do_test  # BASELINE.json's wording
 
-    def do_beam(self, data, width=None, no_repeat_ngram=None, min_length=None, banned_ids=None, length_penalty=None):
+    def do_beam(self, data, width=None, no_repeat_ngram=None, min_length=None, banned_ids=None, length_penalty=None, _enc=None):
         """``do_test`` with beam search instead of the greedy argmax (the reference's common/Generations.py ``beam``: ``width`` hypotheses per
         item ranked by length-normalised cost, retired on EOS): the ``do_test`` dict plus ``beam_score`` [B] (the answer's cum_cost / length),
         ``beam_answers`` [B, W, T] and ``beam_scores`` [B, W] (the best W retired hypotheses, best first; +inf where there are fewer).
         ``min_length`` / ``banned_ids`` as in ``do_test``, for every slot of an item; ``length_penalty`` = alpha (None = the attribute; 1.0 = the
         reference) ranks candidates and retired hypotheses by cum_cost / length^alpha, and ``beam_score`` / ``beam_scores`` are those keys."""
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width,
+        rg, rank = self._respond(data, _enc=_enc, max_target_length=self.max_target_length, beam_width=self.beam_width if width is None else width,
                                  no_repeat_ngram=self._ngram(no_repeat_ngram), decode_rules=self._rules(data, min_length, banned_ids, length_penalty))
         return {'answer': rg[3], 'rank': rank, 'beam_score': rg[5][:, 0], 'beam_answers': rg[4], 'beam_scores': rg[5]}
 
     def do_sample(self, data, num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None, uniforms=None, no_repeat_ngram=None, min_length=None,
-                  banned_ids=None):
+                  banned_ids=None, _enc=None):
         """``do_test`` with every token DRAWN from the model's distribution (the reference's common/Generations.py ``sample`` loop; the draw is
         from the mixed pointer-generator distribution itself after ``temperature`` / ``top_k`` (0 = off) / ``top_p`` (1 = off), not from the
         reference's softmax of it): the ``do_test`` dict plus ``samples`` [B, N, T], ``sample_probs`` [B, N, T] (the model's unfiltered
@@ -309,7 +310,7 @@ class CaSE(nn.Module):
         ``min_length`` / ``banned_ids`` as in ``do_test``, for every sample of an item, zeroed before the cuts and the draw; ``sample_probs``
         stay the model's own probabilities.  With ``min_length`` >= 1 the UNK-for-EOS convention of the first step can no longer fire."""
         sampling = sampling_params(self.vocab2id, num_samples, temperature, top_k, top_p, seed, uniforms)
-        rg, rank = self._respond(data, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram),
+        rg, rank = self._respond(data, _enc=_enc, max_target_length=self.max_target_length, sampling=sampling, no_repeat_ngram=self._ngram(no_repeat_ngram),
                                  decode_rules=self._rules(data, min_length, banned_ids))
         return {'answer': rg[3], 'rank': rank, 'samples': rg[4], 'sample_probs': rg[5], 'sample_scores': rg[6]}
 
@@ -352,6 +353,24 @@ class CaSE(nn.Module):
         out, rank = self._respond(data, score_index=data['response'] if answers is None else answers)
         out['rank'] = rank
         return out
+
+    def do_attribute(self, data, answers="test", trim_eos=None, **decode):
+        """Where an answer came from (eval mode only): which part of the source every answer token was copied from, and the passage the
+        answer cites.  ``answers``: "test" / "beam" / "sample" decode first in that mode (``**decode`` goes to it: ``width``, ``num_samples``,
+        ``no_repeat_ngram``, ...) and the pool is ``answer[:, None]`` / ``beam_answers`` / ``samples``; "response" scores ``data['response']``;
+        an int64 [B, T'] or [B, N, T'] tensor is scored as given.  The encode stages run once.  ``trim_eos``: the ids behind a row's first
+        EOS become PAD before scoring (default: True for a decoded pool -- a fixed-T greedy pass keeps emitting behind EOS --, False
+        otherwise).  -> everything ``do_score`` returns for the pool (``rank``, ``token_probs``, ``copy_probs``, ``scores``, ``loss``,
+        ``tokens``), the decoded pool's own keys, and ``answers`` int64 [B, N, T'] (what was scored); ``copy_mass`` f32 [B, N, T', 1 + P]:
+        the pointer mass of every token from the conversation context (segment 0) and from passage p of the pool (segment 1 + p: column p
+        of ``rank``); ``copy_pos`` int32 [B, N, T']: the position, in ``data['source_map']`` coordinates, of the largest single term (-1:
+        none), ``copy_pos_mass`` that term, ``copy_count`` int32 the source positions that hold the token; ``share`` f32 [B, N, T', 2 + P]:
+        column 0 the generator, clamp(1 - sum_g mass_g / max(p, 1e-30), 0, 1), column 1 + g mass_g / max(p, 1e-30), 0 at PAD; ``support``
+        f32 [B, N, 2 + P]: the mean share over the non-PAD positions; ``cited`` int64 [B, N]: the passage with the largest support as a
+        pool index (the lowest among equals; -1 for an empty answer or no support).  The split is K39 (``ops.copy_attribution``) behind K29
+        on the same operands; more than 63 passages, an unsorted source map, grad enabled or CASE_COPY_ATTRIBUTION=off take the host form.
+        Nothing is read back: a pass at fixed arguments captures into one graph."""
+        return attribute_answers(self, data, lambda: self._encode_select_extract(data), answers, trim_eos, **decode)
 
     def do_rank(self, data):
         """The passage ranking alone (eval mode only): the encoders and the selection stage run, the token-identification stage and the
@@ -411,5 +430,7 @@ class CaSE(nn.Module):
             return self.do_consensus(data)
         elif method == 'rank':
             return self.do_rank(data)
+        elif method == 'attribute':
+            return self.do_attribute(data)
         elif method == 'extract':
             return self.do_extract(data)

@@ -354,6 +354,38 @@ class CumulativeTrainer(object):
         sums = total.tolist()  # (the one read-back of the evaluation)
         return dict({name: s / items for name, s in zip(ops.RANK_METRICS, sums)}, items=items)
 
+    def evaluate_attribution(self, dataset, collate_fn, batch_size, answers="test", labels="passage_label", **decode):
+        """Does the model cite the gold passage?  ``model.do_attribute(data, answers, **decode)`` per batch, the sums of
+        ``evaluation.attribution_ids``' columns (slot 0 of every item's pool) kept on the device, one read-back at the end ->
+        dict(cited_accuracy = the items whose ``cited`` passage is ``data[labels]`` / items -- an item that cites nothing (cited -1) is a
+        miss --, rank_agreement = the items whose cited passage is the one the selection stage ranks first / items, gen_share /
+        context_share / passage_share = the generator's, the conversation context's and all passages' shares of the answers' probability,
+        token-weighted micro-averages, items, tokens = the non-PAD answer tokens counted).  One process, under no_grad in eval mode; the
+        model's mode is restored afterwards."""
+        from ..evaluation.attribution import ATTRIBUTION_COLUMNS, eval_attribution_ids
+        was_training = self.model.training
+        self.model.eval()
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    part = eval_attribution_ids(self.model.do_attribute(data, answers=answers, **decode), data[labels])
+                    total = part if total is None else total + part
+                    items += data[labels].shape[0]
+        finally:
+            self.model.train(was_training)
+        names = ("cited_accuracy", "rank_agreement", "gen_share", "context_share", "passage_share")
+        if items == 0:
+            return dict({name: float('nan') for name in names}, items=0, tokens=0)
+        sums = dict(zip(ATTRIBUTION_COLUMNS, total.tolist()))  # (the one read-back of the evaluation)
+        ratio = lambda a, b: a / b if b else 0.0  # noqa: E731
+        tokens = int(sums["tokens"])
+        return dict(cited_accuracy=sums["cited_hit"] / items, rank_agreement=sums["rank_agree"] / items,
+                    gen_share=ratio(sums["gen_share"], tokens), context_share=ratio(sums["context_share"], tokens),
+                    passage_share=ratio(sums["passage_share"], tokens), items=items, tokens=tokens)
+
     def evaluate_extract(self, dataset, collate_fn, batch_size, top_k=None, select="prior", labels="token_label"):
         """Token-level metrics of the supporting-token stage: ``model.do_extract(data, top_k, select, labels=data[labels])`` per batch (K38
         counts the items while it selects their tokens), the column sums kept on the device, one read-back at the end -> dict(precision =

@@ -17,6 +17,7 @@ import torch
 import torch.nn as nn
 
 from .. import config, ops
+from ..evaluation.attribution import copy_attribution_host
 from .BilinearAttention import BilinearAttention
 from .PositionalEmbedding import PositionalEmbedding
 from .TransformerDecoder import TransformerDecoder, TransformerDecoderLayer
@@ -531,7 +532,7 @@ class PointerDecoderCore(nn.Module):
         setattr(self, mode.counter, steps)
         return mode.result(dec_out)
 
-    def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None):
+    def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None, segments=None):
         """Teacher-forced scoring of given answers (eval mode): ``answers`` int64 [B, T'] or [B, N, T'], ``pad`` marking the positions that
         are not scored.  One full-prefix pass over dec_ids = cat[BOS, answers[:, :-1]] (``_run_prefix``, causal), then the head over row
         chunks of at most ``score_chunk_rows`` (candidate, position) rows.  The N candidates of an item are extra batch rows (``_per_item``).
@@ -540,7 +541,11 @@ class PointerDecoderCore(nn.Module):
         logits, no [rows, V] distribution.  With grad enabled it is the unfused differentiable chain of the training branch (``_generate``,
         ``_mix``, a gather), so gradients reach the parameters.  Nothing is read back: the pass captures into one graph.
         -> dict(token_probs [B, N, T'] (1 where PAD), copy_probs [B, N, T'] (the pointer part, 0 where PAD), scores [B, N] (mean over the
-        scored targets of -log max(p, 1e-30)), loss [1] (sum of -log(p + 1e-8) over the scored targets / their count), tokens int64 scalar)."""
+        scored targets of -log max(p, 1e-30)), loss [1] (sum of -log(p + 1e-8) over the scored targets / their count), tokens int64 scalar).
+        ``segments`` (the G + 1 boundaries of ``evaluation.attribution.source_segments``; None: the launches of a pass without it): every
+        chunk also attributes its targets' pointer mass, K39 (ops.copy_attribution) right behind K29 on the same operands, the host form
+        (``copy_attribution_host``) on the unfused chain, for an unsorted source map, more than 64 segments or CASE_COPY_ATTRIBUTION=off ->
+        also copy_mass f32 [B, N, T', G], copy_pos int32, copy_pos_mass f32 and copy_count int32 [B, N, T']."""
         if self.training:
             raise ValueError("scoring runs in eval mode: call model.eval() first")
         if answers.dim() == 2:
@@ -571,7 +576,10 @@ class PointerDecoderCore(nn.Module):
             chunks = [(r0, min(r0 + step, rows)) for r0 in range(0, rows, step)]
         else:  # an item's rows in several chunks: every chunk lies inside one item
             chunks = [(b * per + o, min(b * per + o + limit, (b + 1) * per)) for b in range(B) for o in range(0, per, limit)]
-        probs, ptrs = [], []
+        probs, ptrs, parts = [], [], []
+        if segments is not None:
+            segments = ops.check_segments(segments, (source_map.ids if sorted_src else source_map).size(1), "scoring", limit=None)
+            kernel = sorted_src and len(segments) - 1 <= ops.ATTRIBUTION_MAX_G and ops.copy_attribution_supported(source_map, len(mems))
         for r0, r1 in chunks:
             n = r1 - r0
             dec_out, gen_in = self._head_parts(dec_in[r0:r1], x[r0:r1], None if feat is None else feat[r0:r1])
@@ -580,6 +588,10 @@ class PointerDecoderCore(nn.Module):
             if fused:  # K29: (max, sum) over the logits row, logit[y], and the pointer mass of y's run in the item's sorted keys
                 logits, mix_logits = self._head_logits(dec_out, gen_in, cx)
                 p, c = ops.pointer_head_score(logits, mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, pad)
+                if segments is not None and kernel:  # K39: the same run of the same keys, kept apart by segment
+                    parts.append(ops.copy_attribution(mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, segments, pad))
+                elif segments is not None:
+                    parts.append(copy_attribution_host(mix_logits, source_map.ids[b0:b1], cp, y, segments, pad, V, max_segments=None))
             else:  # the differentiable chain: every row a batch row of one position, its item's source beside it
                 item = torch.arange(r0, r1, device=dev) // per
                 src = source_map.select(item) if sorted_src else source_map.index_select(0, item)
@@ -592,6 +604,10 @@ class PointerDecoderCore(nn.Module):
                 skip = y.eq(pad) if pad >= 0 else torch.zeros_like(inside)
                 p = torch.where(skip, torch.ones_like(p), torch.where(inside, p, torch.zeros_like(p)))
                 c = torch.where(skip | ~inside, torch.zeros_like(c), c)
+                if segments is not None:  # the host form on the chain's own tensors (the mixing logits are ``_mix``'s)
+                    mix_logits = ops.linear(torch.cat([dec_out] + cx, dim=-1), self.mix.weight, self.mix.bias, out_dtype=torch.float32)
+                    ids = source_map.ids if sorted_src else source_map
+                    parts.append(copy_attribution_host(mix_logits.reshape(n, -1), ids[b0:b1], cp, y, segments, pad, V, max_segments=None))
             probs.append(p)
             ptrs.append(c)
         p, c = torch.cat(probs).view(B, N, T), torch.cat(ptrs).view(B, N, T)
@@ -599,10 +615,15 @@ class PointerDecoderCore(nn.Module):
         count = scored.sum()
         scores = (-torch.log(p.clamp_min(1e-30)) * scored).sum(dim=-1) / scored.sum(dim=-1).clamp_min(1)
         loss = ((-torch.log(p + 1e-8) * scored).sum() / count.clamp_min(1)).reshape(1)
-        return dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
+        out = dict(token_probs=p, copy_probs=c, scores=scores, loss=loss, tokens=count)
+        if segments is not None:
+            whole = {k: torch.cat([part[k] for part in parts]) for k in ("mass", "pos", "pos_mass", "count")}
+            out.update(copy_mass=whole["mass"].view(B, N, T, -1), copy_pos=whole["pos"].view(B, N, T),
+                       copy_pos_mass=whole["pos_mass"].view(B, N, T), copy_count=whole["count"].view(B, N, T))
+        return out
 
     def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None):
+             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None, segments=None):
         """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
         (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) and ``decode_rules`` (what ``decode_rules_param`` returned: min_length,
         banned ids, the beam length penalty) apply to the three decoding modes only."""
@@ -612,7 +633,7 @@ class PointerDecoderCore(nn.Module):
         valid = [m.reshape(B, -1).contiguous() for m in encode_masks]
         weights = None if encode_weights is None else [w.reshape(B, -1) for w in encode_weights]
         if score_index is not None:
-            return self._score(mems, valid, weights, source_map, BOS, score_index, feature_of=feature_of)
+            return self._score(mems, valid, weights, source_map, BOS, score_index, feature_of=feature_of, segments=segments)
         T = groundtruth_index.size(1) if max_target_length is None else max_target_length
         if self.training and groundtruth_index is not None:
             dec_ids = torch.cat([self._bos(B, BOS, dev), groundtruth_index[:, :-1]], dim=-1)
@@ -715,8 +736,8 @@ class TransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0, decode_rules=None):
+                no_repeat_ngram=0, decode_rules=None, segments=None):
         if isinstance(source_maps, (list, tuple)):
             source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
         return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)

@@ -2707,3 +2707,82 @@ def token_select(values, valid, k, scores=None, labels=None):
     if counts is not None:
         out["counts"] = counts
     return out
+
+
+# K39: where the pointer mass of a target token comes from (the per-segment split, the best source position, the run length).  "auto": a
+# device-sorted source map and <= 4 memories; "off": the host form (evaluation.attribution.copy_attribution_host) wherever a pass attributes.
+COPY_ATTRIBUTION = os.environ.get("CASE_COPY_ATTRIBUTION", "auto")
+ATTRIBUTION_MAX_G = 64
+
+
+def copy_attribution_supported(source_map, nmem):
+    return (COPY_ATTRIBUTION != "off" and isinstance(source_map, SortedSource) and 1 <= nmem <= 4
+            and bool(A.lib.case_abi_features() & A.FEAT_COPY_ATTRIBUTION))
+
+
+def check_segments(seg_start, S, who="copy_attribution", limit=ATTRIBUTION_MAX_G):
+    """A Python sequence of segment boundaries, checked in full: 1 .. ``limit`` segments (None: any number), strictly ascending from 0 to S
+    -> list of int."""
+    seg = [int(v) for v in seg_start]
+    G = len(seg) - 1
+    if G < 1 or (limit is not None and G > limit):
+        raise ValueError("%s: 1 .. %s segments (seg_start holds %d boundaries)" % (who, limit, len(seg)))
+    if seg[0] != 0 or seg[-1] != S or any(a >= b for a, b in zip(seg, seg[1:])):
+        raise ValueError("%s: seg_start must ascend strictly from 0 to S = %d (got %r)" % (who, S, seg))
+    return seg
+
+
+def copy_attribution(mix_logits, source_map, rows_per_source, copies, targets, seg_start, pad=0):
+    """K39: mix_logits f32 [R, 1 + nmem]; source_map a SortedSource with R / rows_per_source rows (row r reads key row r // rows_per_source);
+    copies: list of f32 [R, len_k]; targets int64 [R]; seg_start: the G + 1 boundaries that cut the S source positions into G <= 64 segments,
+    a Python sequence (checked in full: strictly ascending from 0 to S) or an int32 device tensor [G + 1] (shape and dtype only: it is not
+    read back) -> dict(mass f32 [R, G]: the pointer mass of the row's target from the positions of each segment; pos int32 [R]: the source
+    position with the largest single term, the lower one among equals; pos_mass f32 [R]: that term; count int32 [R]: the positions of the
+    item's source that hold the target).  ``targets == pad`` (pad -1: none), an id outside [0, V) or absent from the source: 0, -1, 0, 0.
+    No autograd (inference)."""
+    if mix_logits.dim() != 2 or tuple(mix_logits.shape) != (mix_logits.shape[0], len(copies) + 1):
+        raise ValueError("copy_attribution: mix_logits must be [R, 1 + nmem]")
+    if not isinstance(source_map, SortedSource):
+        raise TypeError("copy_attribution: source_map must be a SortedSource (the host form takes plain ids)")
+    R = mix_logits.shape[0]
+    rows_per_source = int(rows_per_source)
+    keys = source_map.keys
+    if rows_per_source < 1 or R % rows_per_source or keys.shape[0] * rows_per_source != R:
+        raise ValueError("copy_attribution: %d rows, %d key rows, rows_per_source %d" % (R, keys.shape[0], rows_per_source))
+    if targets.dtype != torch.int64 or targets.numel() != R:
+        raise TypeError("copy_attribution: targets must be int64 [R]")
+    if not 1 <= len(copies) <= 4:
+        raise ValueError("copy_attribution: 1 .. 4 memories (got %d)" % len(copies))
+    if any(c.dim() != 2 or c.shape[0] != R for c in copies):
+        raise ValueError("copy_attribution: every copies[k] must be [R, len_k]")
+    S = keys.shape[1]
+    if sum(c.shape[1] for c in copies) != S:
+        raise ValueError("copy_attribution: the memories hold %d positions, the source map %d" % (sum(c.shape[1] for c in copies), S))
+    dev = mix_logits.device
+    if torch.is_tensor(seg_start):
+        if seg_start.dtype != torch.int32 or seg_start.dim() != 1 or seg_start.device != dev:
+            raise TypeError("copy_attribution: a seg_start tensor must be int32 [G + 1] on the rows' device")
+        G = seg_start.numel() - 1
+        if not 1 <= G <= ATTRIBUTION_MAX_G:
+            raise ValueError("copy_attribution: 1 .. %d segments (seg_start holds %d boundaries)" % (ATTRIBUTION_MAX_G, G + 1))
+        seg_dev, seg_host = seg_start.contiguous(), None
+    else:
+        seg = check_segments(seg_start, S)
+        G = len(seg) - 1
+        seg_dev, seg_host = None, (C.c_int32 * (G + 1))(*seg)
+    if not bool(A.lib.case_abi_features() & A.FEAT_COPY_ATTRIBUTION):
+        raise RuntimeError("copy_attribution: this build of the library lacks K39 (CASE_FEAT_COPY_ATTRIBUTION)")
+    mix_logits = mix_logits.float().contiguous()
+    cs = [c.float().contiguous() for c in copies]  # (alive until the call)
+    n = len(cs)
+    ptrs = C.cast((C.c_void_p * n)(*[c.data_ptr() for c in cs]), C.c_void_p)
+    lens = C.cast((C.c_int64 * n)(*[c.shape[1] for c in cs]), C.c_void_p)
+    targets = targets.reshape(R).contiguous()
+    mass = torch.empty(R, G, dtype=torch.float32, device=dev)
+    pos = torch.empty(R, dtype=torch.int32, device=dev)
+    pos_mass = torch.empty(R, dtype=torch.float32, device=dev)
+    count = torch.empty(R, dtype=torch.int32, device=dev)
+    A.call("case_copy_attribution", _ptr(mix_logits), _ptr(keys), rows_per_source, ptrs, lens, n, _ptr(targets), int(pad), _ptr(seg_dev),
+           None if seg_host is None else C.cast(seg_host, C.c_void_p), G, _ptr(mass), _ptr(pos), _ptr(pos_mass), _ptr(count), R, source_map.V, S,
+           _stream())
+    return dict(mass=mass, pos=pos, pos_mass=pos_mass, count=count)

@@ -80,7 +80,8 @@ enum {
   CASE_FEAT_RANK_METRICS = 1u << 24,      /* K36 case_rank_metrics */
   CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25, /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
   CASE_FEAT_DECODE_RULES = 1u << 26,      /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
-  CASE_FEAT_TOKEN_LABELS = 1u << 27       /* K37 / K38 case_token_labels / case_token_select */
+  CASE_FEAT_TOKEN_LABELS = 1u << 27,      /* K37 / K38 case_token_labels / case_token_select */
+  CASE_FEAT_COPY_ATTRIBUTION = 1u << 28   /* K39 case_copy_attribution */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -877,6 +878,28 @@ int case_token_labels(const int64_t* passage, const int64_t* response, const voi
                       int64_t B, int64_t P, int64_t L, int64_t T, int64_t F, int64_t pad, case_stream_t stream);
 int case_token_select(const float* values, const uint8_t* valid, const float* scores, const float* labels, int32_t* pos, float* val,
                       int32_t* counts, int64_t B, int64_t S, int32_t K, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Answer attribution (CASE_FEAT_COPY_ATTRIBUTION; purely additive, generation 600 unchanged).
+ * K39 case_copy_attribution: where the pointer mass of a target comes from.  Operands as in K29 (case_pointer_head_score) without the logits:
+ *   mix_logits [R, 1 + nmem] f32, keys [R / rows_per_source, S] (row r reads key row r / rows_per_source), copies / lens with R rows and
+ *   sum lens = S, targets [R] int64, pad (-1: none).  seg_start int32 [G + 1] cuts the source positions 0 .. S - 1 into G segments
+ *   [seg_start[g], seg_start[g + 1]): strictly ascending, seg_start[0] = 0, seg_start[G] = S; the cuts need not coincide with the
+ *   memories'.  With y = targets[r], pm = softmax(mix_logits[r]) (f32, as K29), the run = the source positions s whose id is y and
+ *   term(s) = pm[1 + k(s)] copies[k(s)][r, s - the lengths before k(s)] (an f32 product):
+ *     mass[r, g]  f32  the sum of term(s) over the run's positions in segment g (f64 per lane, a fixed tree, rounded once)
+ *     pos[r]      int32  the run's position with the largest term, the LOWER position among equal terms (an all-zero run: its first)
+ *     pos_mass[r] f32  that term        count[r] int32  the length of the run
+ *   y == pad, y outside [0, V) or a y the item's source does not hold: mass 0, pos -1, pos_mass 0, count 0.
+ *   The boundaries come from `seg_start_host` (host memory: checked here, CASE_E_ARG when they do not ascend from 0 to S, and handed to the
+ *   kernel by value; `seg_start` is then ignored) or, when that is NULL, from `seg_start` in DEVICE memory, which is not read back: the
+ *   caller has checked it (whatever it holds, the kernel reads and writes inside its operands).  One wave per row, no logits row is read,
+ *   no atomics: two launches give the same bits.  nmem <= 4, S <= 32768, V <= 131071, 1 <= G <= 64, or CASE_E_UNSUPPORTED.
+ *   Asynchronous on `stream`; every output element is written.
+ * ------------------------------------------------------------------------------------------- */
+int case_copy_attribution(const float* mix_logits, const uint32_t* keys, int64_t rows_per_source, const float* const* copies, const int64_t* lens,
+                          int32_t nmem, const int64_t* targets, int64_t pad, const int32_t* seg_start, const int32_t* seg_start_host, int32_t G,
+                          float* mass, int32_t* pos, float* pos_mass, int32_t* count, int64_t R, int64_t V, int64_t S, case_stream_t stream);
 
 #ifdef __cplusplus
 }
