@@ -325,6 +325,79 @@ class CumulativeTrainer(object):
             return dict(bleu=float('nan'), items=0)
         return dict(bleu=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
 
+    def evaluate_meteor(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False, classes=None):
+        """METEOR of ``model(data, method)['answer']`` against ``data[references]`` (as ``evaluate_rouge`` takes them), without building a Python
+        string: ``evaluation.eval_meteor_ids`` per batch (K40: nltk's ``meteor_score`` with default parameters, its exact stage on ids and
+        ``classes`` -- an int32 [V] table id -> equivalence class, None: exact matches only -- in place of its stem and synonym stages; the
+        best score over the present ground truths of an item), the sum kept on the device, one read-back at the end -> dict(meteor = the
+        mean of the per-item METEOR x 100 rounded to 2 decimals -- ``evaluation.eval_meteor``'s number for ``predict`` + ``to_sentence``, what
+        the reference's ``eval_meteor_file`` prints for the same tokens and the same stages --, items = the items counted).
+        ``remove_duplicates`` as in ``evaluate_rouge``.  One process, under no_grad in eval mode; the model's mode is restored afterwards."""
+        from ..evaluation.meteor_ids import eval_meteor_ids
+        from ..evaluation.rouge_ids import model_specials
+        was_training = self.model.training
+        self.model.eval()
+        specials = model_specials(self.model.vocab2id)
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    out = self.model(data, method=method)
+                    if classes is not None and classes.device != out['answer'].device:
+                        classes = classes.to(out['answer'].device)
+                    part = eval_meteor_ids(out['answer'], data[references], specials, classes, remove_duplicates=remove_duplicates).sum()
+                    total = part if total is None else total + part
+                    items += out['answer'].shape[0]
+        finally:
+            self.model.train(was_training)
+        if items == 0:
+            return dict(meteor=float('nan'), items=0)
+        return dict(meteor=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
+
+    GENERATION_METRICS = ('rouge_l', 'bleu', 'meteor')
+
+    def evaluate_generation(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False,
+                            metrics=GENERATION_METRICS, classes=None):
+        """The answer-quality line of ``Run_Evaluation`` from ONE decoding pass: per batch ``model(data, method)`` runs once and every metric
+        named in ``metrics`` ('rouge_l', 'bleu', 'meteor') is computed from that pass's ``answer`` with the per-item function its
+        single-metric method uses (``eval_rouge_l_ids``, ``eval_bleu_ids``, ``eval_meteor_ids``), the sums kept on the device, one read-back
+        at the end -> dict(one entry per named metric, rounded exactly as ``evaluate_rouge`` / ``evaluate_bleu`` / ``evaluate_meteor`` round
+        it, items = the items counted).  An unknown metric name is a ``ValueError`` before anything is decoded.  ``remove_duplicates`` and
+        ``classes`` as in those methods.  One process, under no_grad in eval mode; the model's mode is restored afterwards."""
+        from ..evaluation.meteor_ids import eval_meteor_ids
+        from ..evaluation.ngram_ids import eval_bleu_ids
+        from ..evaluation.rouge_ids import eval_rouge_l_ids, model_specials
+        metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
+        unknown = [name for name in metrics if name not in self.GENERATION_METRICS]
+        if unknown or not metrics:
+            raise ValueError("evaluate_generation: metrics must name some of %s, not %r" % (self.GENERATION_METRICS, metrics))
+        was_training = self.model.training
+        self.model.eval()
+        specials = model_specials(self.model.vocab2id)
+        per_item = dict(rouge_l=lambda hyp, ref: eval_rouge_l_ids(hyp, ref, specials, remove_duplicates),
+                        bleu=lambda hyp, ref: eval_bleu_ids(hyp, ref, specials, remove_duplicates=remove_duplicates),
+                        meteor=lambda hyp, ref: eval_meteor_ids(hyp, ref, specials, classes, remove_duplicates=remove_duplicates))
+        total, items = None, 0
+        try:
+            with torch.no_grad():
+                loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
+                                                     pin_memory=torch.cuda.is_available())
+                for data in DevicePrefetcher(loader):
+                    out = self.model(data, method=method)
+                    if classes is not None and classes.device != out['answer'].device:
+                        classes = classes.to(out['answer'].device)
+                    part = torch.stack([per_item[name](out['answer'], data[references]).sum() for name in metrics])
+                    total = part if total is None else total + part
+                    items += out['answer'].shape[0]
+        finally:
+            self.model.train(was_training)
+        if items == 0:
+            return dict({name: float('nan') for name in metrics}, items=0)
+        sums = total.tolist()  # (the one read-back of the evaluation)
+        return dict({name: round(s / items, 2) for name, s in zip(metrics, sums)}, items=items)
+
     def evaluate_rank(self, dataset, collate_fn, batch_size, method='rank', labels='passage_label', keys=None, valid=None):
         """The TREC ranking metrics of ``model(data, method)['rank']`` [B, P] against ``data[labels]`` (int64 [B]: the index of the gold
         passage; or an integer [B, P] tensor of grades), every item its own query: ``evaluation.eval_rank_ids`` per batch (K36), the column

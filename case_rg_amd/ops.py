@@ -2598,6 +2598,53 @@ def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
     return pair, bleu, bp
 
 
+# K40: METEOR on token ids
+METEOR_MAX_T = 256
+
+
+def meteor_supported(Ta):
+    """Hypotheses of Ta positions: K40 holds a hypothesis in 4 x 64 match-mask bits."""
+    return 1 <= Ta <= METEOR_MAX_T and bool(A.lib.case_abi_features() & A.FEAT_METEOR)
+
+
+def meteor(a, a_len, b, b_len, classes=None, alpha=0.9, beta=3.0, gamma=0.5, want_align=False):
+    """K40: a int64 [B, N, Ta] / a_len int32 [B, N] (front-packed hypotheses and their lengths, as ``sentence_compact`` writes them), b int64
+    [B, M, Tb] / b_len int32 [B, M] (references; ``b_len`` 0: absent) -> dict(counts int32 [B, N, M, 3] = (matches, exact matches, chunks) of
+    evaluation.meteor's alignment, meteor_pair f32 [B, N, M] = the score of every pair (f64 rounded once), meteor f64 [B, N] = the maximum over
+    the present references, best_ref int32 [B, N] = the lowest index that reaches it (-1 without a present reference) and, with
+    ``want_align``, align int32 [B, N, M, Ta] = the matched reference position of every hypothesis position or -1).  ``classes``: an int32 [V]
+    table id -> equivalence class on the ids' device (a negative entry and an id >= V: no class) for the second stage; None: exact matches
+    only.  Ta <= 256; ids must lie in [0, 2^31) (not checked: compared on 32 bits)."""
+    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
+        raise TypeError("meteor: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
+    B, N, Ta = a.shape
+    M, Tb = b.shape[1], b.shape[2]
+    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
+        raise TypeError("meteor: the lengths must be int32 [B, N] and [B, M]")
+    if Ta > METEOR_MAX_T:
+        raise ValueError("meteor: hypotheses of up to %d positions (got %d)" % (METEOR_MAX_T, Ta))
+    try:
+        alpha, beta, gamma = float(alpha), float(beta), float(gamma)
+    except (TypeError, ValueError):
+        raise ValueError("meteor: alpha, beta and gamma must be numbers (got %r, %r, %r)" % (alpha, beta, gamma))
+    if not (0.0 <= alpha <= 1.0 and 0.0 <= gamma <= 1.0 and 0.0 <= beta < math.inf):
+        raise ValueError("meteor: alpha and gamma in [0, 1], beta >= 0 and finite (got %r, %r, %r)" % (alpha, beta, gamma))
+    if classes is not None and (not torch.is_tensor(classes) or classes.dtype != torch.int32 or classes.dim() != 1 or classes.numel() == 0
+                                or classes.device != a.device):
+        raise ValueError("meteor: classes must be a 1-D int32 tensor [V] on the ids' device")
+    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
+    classes = None if classes is None else classes.contiguous()
+    out = dict(counts=torch.empty(B, N, M, 3, dtype=torch.int32, device=a.device),
+               meteor_pair=torch.empty(B, N, M, dtype=torch.float32, device=a.device),
+               meteor=torch.empty(B, N, dtype=torch.float64, device=a.device), best_ref=torch.empty(B, N, dtype=torch.int32, device=a.device))
+    if want_align:
+        out["align"] = torch.empty(B, N, M, Ta, dtype=torch.int32, device=a.device)
+    A.call("case_meteor", _ptr(a), _ptr(a_len), _ptr(b), _ptr(b_len), _ptr(classes), 0 if classes is None else classes.numel(), alpha, beta,
+           gamma, _ptr(out["counts"]), _ptr(out["meteor_pair"]), _ptr(out["meteor"]), _ptr(out["best_ref"]), _ptr(out.get("align")), B, N, M,
+           Ta, Tb, _stream())
+    return out
+
+
 # K36: TREC ranking metrics of score rows
 RANK_MAX_P, RANK_MAX_JUDGED = 1024, 2048
 RANK_CUTOFFS = (5, 10, 15, 20, 30, 100, 200, 500, 1000)

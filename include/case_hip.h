@@ -81,7 +81,8 @@ enum {
   CASE_FEAT_POINTER_HEAD_WIDE = 1u << 25, /* the global-row forms of K23 / K24 / K28: case_pointer_head_decode_wide / _beam_wide / _sample_wide */
   CASE_FEAT_DECODE_RULES = 1u << 26,      /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
   CASE_FEAT_TOKEN_LABELS = 1u << 27,      /* K37 / K38 case_token_labels / case_token_select */
-  CASE_FEAT_COPY_ATTRIBUTION = 1u << 28   /* K39 case_copy_attribution */
+  CASE_FEAT_COPY_ATTRIBUTION = 1u << 28,  /* K39 case_copy_attribution */
+  CASE_FEAT_METEOR = 1u << 29             /* K40 case_meteor */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -900,6 +901,31 @@ int case_token_select(const float* values, const uint8_t* valid, const float* sc
 int case_copy_attribution(const float* mix_logits, const uint32_t* keys, int64_t rows_per_source, const float* const* copies, const int64_t* lens,
                           int32_t nmem, const int64_t* targets, int64_t pad, const int32_t* seg_start, const int32_t* seg_start_host, int32_t G,
                           float* mass, int32_t* pos, float* pos_mass, int32_t* count, int64_t R, int64_t V, int64_t S, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * METEOR on token ids (CASE_FEAT_METEOR; purely additive, generation 600 unchanged).  The metric is nltk's meteor_score, which
+ * evaluation/Eval_Meteor.py calls, with its exact stage on ids and its stem / synonym stages as ONE caller-provided table of equivalence
+ * classes; evaluation/meteor.py states the rule.
+ * K40 case_meteor: a, a_len, b, b_len exactly as case_lcs_pairs takes them (front-packed ids, lengths clamped to 0 .. Ta / Tb, ids compared
+ *   on their low 32 bits, Ta <= 256 or CASE_E_UNSUPPORTED, Tb without such a limit).  For hypothesis h = a[b, n, 0 .. la) and reference
+ *   r = b[b, m, 0 .. lb):
+ *     stage 1: for i = la - 1 .. 0, the LAST still-unmatched j with r[j] == h[i] is matched to i;
+ *     stage 2 (classes != NULL: int32 [V] in device memory, id -> class): the same over the positions stage 1 left, comparing classes[id]; an
+ *              id outside [0, V) or with a negative entry has no class and never matches here.  classes == NULL requires V == 0;
+ *     chunks:  over the matches sorted by i, 1 + the number of consecutive pairs (i, j), (i', j') that are not i' == i + 1 and j' == j + 1;
+ *     score:   with mt = the number of matches, 0 when mt == 0, else P = mt / la, R = mt / lb, fmean = P R / (alpha P + (1 - alpha) R),
+ *              pen = gamma pow(chunks / mt, beta), score = (1 - pen) fmean, in f64 in this order without contraction.
+ *   counts int32 [B, N, M, 3] = (mt, the matches of stage 1, chunks), all 0 for an absent reference (lb == 0) and for la == 0; chunks 0 when
+ *   mt == 0.  meteor_pair f32 [B, N, M] = the score rounded once.  meteor f64 [B, N] = the maximum over the present references, best_ref
+ *   int32 [B, N] the lowest index that reaches it; 0 and -1 without a present reference.  align int32 [B, N, M, Ta] (may be NULL) = the matched
+ *   reference position of every hypothesis position, -1 where there is none.
+ *   alpha and gamma in [0, 1], beta >= 0, all finite (CASE_E_ARG otherwise); nltk's defaults are 0.9, 3.0, 0.5.
+ *   One wave per hypothesis, no atomics, integer arithmetic up to the one score evaluation: two launches give the same bits.
+ *   Asynchronous on `stream`; every output element is written.
+ * ------------------------------------------------------------------------------------------- */
+int case_meteor(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, const int32_t* classes, int64_t V, double alpha,
+                double beta, double gamma, int32_t* counts, float* meteor_pair, double* meteor, int32_t* best_ref, int32_t* align, int64_t B,
+                int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream);
 
 #ifdef __cplusplus
 }
