@@ -394,7 +394,14 @@ __global__ __launch_bounds__(NTHR) void fwd_kernel(const Args a) {
     for (int t = 0; t < 3; ++t)
 #pragma unroll
       for (int e = (t == 0 ? 3 : 0); e + 1 < 16; e += 2) mx = fmaxf(fmaxf(mx, st[t][e]), st[t][e + 1]);
-    mx = fmaxf(fmaxf(mx, st[1][15]), st[2][15]);  // (tile 0 ends on an odd count: its register 15 was taken in the loop)
+    // Tile 0 enters the loop at register 3, so the loop stops in front of its register 15 (keys 27 / 31 of the chunk; tiles 1 and 2 are
+    // covered whole): the maximum above is over 47 of the 48 scores.  Within the lazy-rescale threshold a reference below the true maximum
+    // costs nothing, so the missing score joins the way the reference maximum moves between chunks: only when it leads the others by more
+    // than THR (a row whose only unmasked key of the chunk is this one: mx = -inf, and the score is taken).  Beyond that exp2(s - m) would
+    // grow without bound and overflow at a lead of 127.  This lag and the lazy rescale's can add up: a probability is exp2 of at most
+    // 2 THR (e^16), exact enough in f32 and in bf16.  The plain 48-way maximum would do as well, but it moves the bits of every row whose
+    // leader is this score, and the production-geometry bf16 fixtures are pinned to the bits as they are.
+    mx = (st[0][15] * scale2 > mx * scale2 + RESCALE_THR) ? st[0][15] : mx;
     // hipcc moves register-only arithmetic across s_barrier (IR-level sinking towards the use): values that must exist when the
     // interval closes pass through an empty asm
     asm volatile("" : "+v"(mx), "+v"(st[0]), "+v"(st[1]), "+v"(st[2]));

@@ -181,13 +181,14 @@ __global__ __launch_bounds__(NTHR) void gemm_small_kernel(const Args g, const in
   E.C = reinterpret_cast<OutT*>(g.C); E.aux = reinterpret_cast<const bf16_t*>(g.aux); E.aux_out = reinterpret_cast<bf16_t*>(g.aux_out);
   E.bias_row = g.bias_row; E.bias_col = g.bias_col; E.ldc = g.ldc; E.ld_aux = g.ld_aux; E.M = g.M; E.N = g.N;
   E.alpha = g.alpha; E.drop_p = g.drop_p; E.drop_scale = (epi & CASE_EPI_DROPOUT) ? 1.f / (1.f - g.drop_p) : 1.f;
-  E.seed = g.seed; E.rng_base = g.offset + rng_base_of(g.state); E.epi = epi;
+  E.seed = g.seed; E.rng_base = g.offset + rng_base_of(g.state);
+  E.epi = (split == 0) ? epi : (epi & ~(CASE_EPI_BIAS_COL | CASE_EPI_BIAS_ROW));  // split-K: the biases arrive once (as in gemm_impl.inc)
 #pragma unroll
   for (int i = 0; i < 2; ++i)
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
       const int64_t col = n0 + wc * 32 + j * 16 + (l & 15);
-      const float bc = (epi & CASE_EPI_BIAS_COL) ? g.bias_col[col] : 0.f;
+      const float bc = (E.epi & CASE_EPI_BIAS_COL) ? g.bias_col[col] : 0.f;
 #pragma unroll
       for (int e = 0; e < 4; ++e) E.emit(acc[i][j][e], m0 + wr * 32 + i * 16 + 4 * (l >> 4) + e, col, bc);
     }

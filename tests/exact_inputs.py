@@ -1,0 +1,374 @@
+"""Operands for which the MFMA GEMM and the attention kernels have no rounding to hide behind: every product and every partial sum is
+exactly representable in f32, so the result does not depend on the summation order, the tiling, the split or the use of f32 atomics, and a
+kernel must equal the float64 restatement in every bit (after ONE round-to-nearest-even where the output is bf16).
+
+Plain torch, no GPU: everything is built on the CPU in float64 (the values are small integers or powers of two, exact in bf16 and f32) and the
+callers move it where they need it.  tests/test_exact_inputs_cpu.py pins every claim made here for the seeds the GPU tests use.
+
+GEMM       integers in [-15, 15], an eighth of them 0: |product| <= 225, and K * 225 < 2^24 for every K used.
+attention  the first C <= min(d, 8) head dimensions carry a class code: key j of class c has 2^10 at dimension c, query i of class c has
+           -2^10 at every code dimension but c.  A score is 0 inside the class and -2^20 outside (exp of it, times any 1/sqrt(d), is 0 in
+           f32), so the probabilities are exactly 1/n on the n valid keys of the class.  Class sizes are the powers of two of the binary
+           decomposition of the valid length, scattered over the positions by a seeded permutation per (item, head).  V is integers in
+           [-127, 127]; O is the exact class mean."""
+import torch
+
+F64 = torch.float64
+GEMM_BOUND = 15
+CODE = 1024.0  # 2^10
+V_BOUND = 127
+DO_BOUND = 3
+
+
+def _gen(seed):
+    return torch.Generator().manual_seed(seed)
+
+
+def ints(shape, seed, bound=GEMM_BOUND, zero_share=0.125):
+    """float64 integers in [-bound, bound]; ``zero_share`` of them forced to 0."""
+    g = _gen(seed)
+    x = torch.randint(-bound, bound + 1, tuple(shape), generator=g)
+    z = torch.rand(tuple(shape), generator=g) < zero_share
+    return torch.where(z, torch.zeros_like(x), x).to(F64)
+
+
+def signs(shape, seed):
+    """Integers in [-15, 15] with a third each positive, zero and negative (the operand of MUL_DRELU)."""
+    g = _gen(seed)
+    s = torch.randint(-1, 2, tuple(shape), generator=g)
+    return (s * torch.randint(1, GEMM_BOUND + 1, tuple(shape), generator=g)).to(F64)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# GEMM
+# ---------------------------------------------------------------------------------------------------------------------------------
+LAYOUTS = {"nt": (False, False), "nn": (False, True), "tn": (True, True), "tt": (True, False)}  # name -> (a_kmajor, b_kmajor)
+
+
+def gemm_exact_k(K):
+    return K * GEMM_BOUND * GEMM_BOUND < 2 ** 24
+
+
+def gemm_operands(layout, M, N, K, seed):
+    """(a, b) as stored: A is [M, K] (or [K, M] k-major), B is [N, K] (or [K, N] k-major)."""
+    assert gemm_exact_k(K)
+    ak, bk = LAYOUTS[layout]
+    return ints((K, M) if ak else (M, K), 2 * seed + 1), ints((K, N) if bk else (N, K), 2 * seed + 2)
+
+
+def gemm_product(layout, a, b):
+    """op(A) op(B) of the stored operands, in the dtype they come in."""
+    ak, bk = LAYOUTS[layout]
+    return (a.t() if ak else a) @ (b if bk else b.t())
+
+
+def epilogue(acc, alpha=1.0, bias_col=None, bias_row=None, relu=False, drelu_aux=None, keep=None, residual=None):
+    """The documented order: alpha * acc + bias -> RELU -> MUL_DRELU -> DROPOUT (p = 0.5: scale 2) -> + RESIDUAL.  Returns (result,
+    the value in front of the activation)."""
+    v = alpha * acc
+    if bias_col is not None:
+        v = v + bias_col[None, :]
+    if bias_row is not None:
+        v = v + bias_row[:, None]
+    pre = v
+    if relu:
+        v = v.clamp_min(0.0)
+    if drelu_aux is not None:
+        v = torch.where(drelu_aux > 0, v, torch.zeros_like(v))
+    if keep is not None:
+        v = 2.0 * keep.to(v.dtype) * v
+    if residual is not None:
+        v = v + residual
+    return v, pre
+
+
+def round_bf16(ref):
+    """The ONE rounding a bf16 output is allowed: float64 -> f32 (exact for everything built here) -> bf16, to nearest even."""
+    f = ref.to(torch.float32)
+    assert torch.equal(f.to(F64), ref), "the reference is not exact in f32"
+    return f.to(torch.bfloat16)
+
+
+def bf16_inexact_and_ties(ref):
+    """(share of the elements that are not representable in bf16, number of exact ties between two bf16 neighbours)."""
+    low = ref.to(torch.float32).contiguous().view(torch.int32) & 0xFFFF
+    return (low != 0).double().mean().item(), int((low == 0x8000).sum())
+
+
+def shuffled_f32_gemm(layout, a, b, order_seed, splits):
+    """The same product accumulated in f32 with the K index permuted and cut into ``splits`` partial sums that are added one after
+    another (what split-K with atomics does, in one of its orders)."""
+    ak, bk = LAYOUTS[layout]
+    A, B = (a.t() if ak else a).float(), (b if bk else b.t()).float()
+    K = A.shape[1]
+    perm = torch.randperm(K, generator=_gen(order_seed))
+    out = torch.zeros(A.shape[0], B.shape[1], dtype=torch.float32)
+    for idx in perm.chunk(max(1, min(splits, K))):
+        out = out + A[:, idx] @ B[idx, :]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# attention
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pow2_parts(n):
+    """Binary decomposition, largest first: 292 -> [256, 32, 4]."""
+    return [1 << b for b in range(n.bit_length() - 1, -1, -1) if n >> b & 1]
+
+
+def cut_length(Lk):
+    """A valid length strictly inside the memory that ends in the middle of every tile (odd), with at most four powers of two."""
+    if Lk < 16:
+        return max(1, Lk // 2)
+    cut = Lk * 5 // 8
+    while bin(cut).count("1") > 2:
+        cut &= cut - 1
+    return cut | 5
+
+
+def ragged_lengths(Lk, N=4):
+    """One item full, one cut mid-tile, one with a single valid key, one with none; further items repeat the pattern."""
+    base = [Lk, cut_length(Lk), 1, 0]
+    return [base[i % 4] for i in range(N)]
+
+
+class AttnCase(object):
+    """q [N, Lq, h d], k / v [N, Lk, h d] float64, key_valid [N, Lk] bool, key_class [N, h, Lk] (-1: not a valid key), query_class
+    [N, h, Lq] (-1: no visible key: a row of zeros), marked [N, h, Lq] (causal rows whose visible count is no power of two)."""
+
+    def probabilities(self, device="cpu"):
+        """P [N, h, Lq, Lk] float64: exactly 1 / n on the n valid, visible keys of the query's class (not exact on marked rows)."""
+        kc, qc = self.key_class.to(device), self.query_class.to(device)
+        match = (kc[:, :, None, :] == qc[:, :, :, None]) & (qc[:, :, :, None] >= 0)
+        if self.causal:
+            Lq, Lk = qc.shape[2], kc.shape[2]
+            match &= torch.ones(Lq, Lk, dtype=torch.bool, device=device).tril()
+        n = match.sum(-1, keepdim=True)
+        return match.to(F64) / n.clamp_min(1).to(F64)
+
+    def heads(self, t):
+        """[N, L, h d] -> [N, h, L, d]"""
+        N, L, _ = t.shape
+        return t.reshape(N, L, self.h, self.d).transpose(1, 2)
+
+    def merge(self, t):
+        """[N, h, L, d] -> [N, L, h d]"""
+        N, h, L, d = t.shape
+        return t.transpose(1, 2).reshape(N, L, h * d)
+
+    def output(self, device="cpu"):
+        """O [N, Lq, h d] float64 = P V (every sum is an integer over a power of two: exact in float64 and in f32)."""
+        return self.merge(self.probabilities(device) @ self.heads(self.v.to(device)))
+
+    def backward(self, dO, scale, o_read=None, device="cpu"):
+        """(dQ, dK, dV, |dS| |K| row sums) in float64 for the gradient dO [N, Lq, h d].  ``o_read``: the output the kernel reads for
+        delta = rowsum(dO * O) (the fused kernels read their own bf16 result); None = rowsum(P * dP), the softmax backward's form."""
+        P = self.probabilities(device)
+        qh, kh, vh, gh = [self.heads(t.to(device).to(F64)) for t in (self.q, self.k, self.v, dO)]
+        dV = P.transpose(-1, -2) @ gh
+        dP = gh @ vh.transpose(-1, -2)
+        delta = (P * dP).sum(-1, keepdim=True) if o_read is None else (gh * self.heads(o_read.to(device).to(F64))).sum(-1, keepdim=True)
+        dS = P * (dP - delta)
+        dQ, dK = scale * (dS @ kh), scale * (dS.transpose(-1, -2) @ qh)
+        bound_q = scale * (dS.abs() @ kh.abs())
+        return self.merge(dQ), self.merge(dK), self.merge(dV), self.merge(bound_q)
+
+
+def _ranks(valid_h, g):
+    """valid_h [N, h, L] -> rank of every valid position in a seeded permutation of the valid positions of its (item, head)."""
+    r = torch.rand(valid_h.shape, generator=g, dtype=F64)
+    r = torch.where(valid_h, r, r + 2.0)
+    return r.argsort(-1).argsort(-1)
+
+
+def attention_case(N, h, Lq, Lk, d, seed, lengths=None, causal=False, mode="classes", max_classes=8, v_bound=V_BOUND):
+    """``mode``: "classes" (the general case), "class_const" (backward case A: V constant within every class), "uniform" (backward
+    case B: Q = 0 and a power-of-two number of valid keys scattered inside the valid prefix: the uniform softmax)."""
+    g = _gen(seed)
+    lengths = list(ragged_lengths(Lk, N) if lengths is None else lengths)
+    assert len(lengths) == N and all(0 <= n <= Lk for n in lengths) and (not causal or Lq == Lk)
+    cmax = min(d, max_classes, 8)
+    pos = torch.arange(Lk)
+    valid = pos[None, :] < torch.tensor(lengths)[:, None]                                   # [N, Lk]
+    if mode == "uniform":  # keep the largest power of two of the prefix, scattered
+        keep = torch.tensor([0 if n == 0 else 1 << (n.bit_length() - 1) for n in lengths])
+        valid = valid & (_ranks(valid[:, None, :], g)[:, 0, :] < keep[:, None])
+        counts = keep.tolist()
+    else:
+        counts = lengths
+    valid_h = valid[:, None, :].expand(N, h, Lk)
+    rank = _ranks(valid_h, g)
+    parts = [[] if mode == "uniform" and n else pow2_parts(n) for n in counts]
+    parts = [p if p else ([n] if n else []) for p, n in zip(parts, counts)]
+    assert all(len(p) <= cmax for p in parts), "valid lengths %s need more than %d classes" % (counts, cmax)
+    ncls = torch.tensor([max(1, len(p)) for p in parts])                                    # [N]
+    bounds = torch.full((N, 8), 1 << 40, dtype=torch.int64)
+    for n, p in enumerate(parts):
+        if p:
+            bounds[n, :len(p)] = torch.tensor(p).cumsum(0)
+    key_class = (rank[..., None] >= bounds[:, None, None, :]).sum(-1)                       # [N, h, Lk]: class by rank for the valid keys
+    noise = torch.randint(0, 1 << 30, (N, h, Lk), generator=g) % ncls[:, None, None]        # masked keys carry a code as well: the mask must count
+    key_code = torch.where(valid_h, key_class, noise)
+    key_class = torch.where(valid_h, key_class, torch.full_like(key_class, -1))
+    if mode == "uniform":  # the codes in K are free (Q = 0): spread them, dQ = scale dS K then sees every code dimension
+        key_code = torch.randint(0, cmax, (N, h, Lk), generator=g)
+    marked = torch.zeros(N, h, Lq, dtype=torch.bool)
+    if causal:
+        onehot = key_class[..., None] == torch.arange(8)                                    # [N, h, L, 8]
+        cnt = onehot.cumsum(2)                                                              # visible valid keys of each class for query i
+        pow2 = (cnt > 0) & ((cnt & (cnt - 1)) == 0)
+        pick = torch.rand(N, h, Lq, 8, generator=g, dtype=F64) + 1.0
+        best2, best1 = (pick * pow2).max(-1), (pick * (cnt > 0)).max(-1)
+        query_class = torch.where(best2.values > 0, best2.indices, best1.indices)
+        marked = (best2.values == 0) & (best1.values > 0)
+        query_class = torch.where(best1.values > 0, query_class, torch.full_like(query_class, -1))
+    else:
+        query_class = torch.randint(0, 1 << 30, (N, h, Lq), generator=g) % ncls[:, None, None]
+        query_class = torch.where(torch.tensor(counts)[:, None, None] > 0, query_class, torch.full_like(query_class, -1))
+    dims = torch.arange(d)
+    k = torch.where(key_code[..., None] == dims, CODE, 0.0).to(F64)                        # [N, h, Lk, d]
+    if mode == "uniform":
+        q = torch.zeros(N, h, Lq, d, dtype=F64)
+        query_class = torch.where(query_class >= 0, torch.zeros_like(query_class), query_class)
+    else:
+        coded = (dims < ncls[:, None, None, None]) & (dims != query_class[..., None]) & (query_class[..., None] >= 0)
+        q = torch.where(coded, -CODE, 0.0).to(F64)                                          # [N, h, Lq, d]
+    v = ints((N, h, Lk, d), seed + 7919, bound=v_bound, zero_share=0.0)
+    if mode == "class_const":
+        table = ints((N, h, 8, d), seed + 104729, bound=v_bound, zero_share=0.0)
+        v = torch.gather(table, 2, key_code[..., None].expand(N, h, Lk, d))
+    c = AttnCase()
+    c.N, c.h, c.Lq, c.Lk, c.d, c.causal, c.mode, c.lengths = N, h, Lq, Lk, d, causal, mode, lengths
+    c.q, c.k, c.v = c.merge(q), c.merge(k), c.merge(v)
+    c.key_valid, c.key_class, c.query_class, c.marked = valid, key_class, query_class, marked
+    return c
+
+
+def grad_output(case, seed):
+    """dO [N, Lq, h d]: integers in [-3, 3]; zero on the marked rows of a causal case.  A marked row's probabilities are not exact, but
+    with dO = 0 it adds exactly nothing to dV = P^T dO and its dS = P (dP - delta) is exactly 0, so dV is again integers over powers of two
+    -- and still sees every key of every unmarked row: a kernel that let a query look past the diagonal gets another P, another dV."""
+    g = ints((case.N, case.Lq, case.h * case.d), seed, bound=DO_BOUND, zero_share=0.0)
+    return g * case.merge((~case.marked)[..., None].expand(case.N, case.h, case.Lq, case.d).to(F64))
+
+
+def scores(case):
+    """S [N, h, Lq, Lk] float64 = Q K^T without the 1/sqrt(d): exactly 0 inside the class, -2^20 times a positive integer outside."""
+    return case.heads(case.q) @ case.heads(case.k).transpose(-1, -2)
+
+
+def softmax_f32(case, scale, order_seed):
+    """The probabilities as a kernel gets them, in f32 and with the keys visited in a shuffled order: online softmax over chunks."""
+    s = (scores(case).float() * torch.tensor(scale, dtype=torch.float32))
+    allowed = case.key_valid[:, None, None, :].expand_as(s).clone()
+    if case.causal:
+        allowed &= torch.ones(case.Lq, case.Lk, dtype=torch.bool).tril()
+    s = torch.where(allowed, s, torch.full_like(s, float("-inf")))
+    perm = torch.randperm(case.Lk, generator=_gen(order_seed))
+    m = torch.full(s.shape[:-1], float("-inf"))
+    l = torch.zeros(s.shape[:-1])
+    for idx in perm.chunk(max(1, min(5, case.Lk))):
+        blk = s[..., idx]
+        m_new = torch.maximum(m, blk.max(-1).values)
+        safe = torch.where(torch.isinf(m_new), torch.zeros_like(m_new), m_new)
+        l = l * torch.exp(torch.where(torch.isinf(m), torch.full_like(m, float("-inf")), m - safe)) + torch.exp(blk - safe[..., None]).sum(-1)
+        m = m_new
+    safe = torch.where(torch.isinf(m), torch.zeros_like(m), m)
+    p = torch.exp(s - safe[..., None]) / l.clamp_min(1e-30)[..., None]
+    return torch.where(allowed, p, torch.zeros_like(p))
+
+
+def mqa_case(B, S, seed, lengths=None, heads=8, width=512):
+    """K21's operands: memory [B, S, 512] is key AND value -- the class code in its first 8 columns, integers in [-127, 127] in the rest;
+    qp [B, 8 * 512] is the absorbed query, -2^10 on the code columns of the other classes.  Returns (AttnCase with h = 1 holding the
+    memory as k and v, qp, query_class [B, heads])."""
+    c = attention_case(B, 1, 1, S, width, seed, lengths=lengths)
+    mem = c.v.clone()
+    mem[:, :, :8] = c.k[:, :, :8]
+    c.k = c.v = mem
+    g = _gen(seed + 31)
+    ncls = torch.tensor([max(1, bin(n).count("1")) for n in c.lengths])
+    qc = torch.randint(0, 1 << 30, (B, heads), generator=g) % ncls[:, None]
+    cols = torch.arange(width)
+    qp = torch.where((cols < ncls[:, None, None]) & (cols != qc[..., None]), -CODE, 0.0).to(F64)  # [B, heads, width]
+    return c, qp.reshape(B, heads * width), qc
+
+
+def mqa_output(c, qc, device="cpu"):
+    """[B, heads * 512] float64: per head the mean of the memory rows of the head's class."""
+    kc = c.key_class[:, 0, :].to(device)                                                   # [B, S]
+    match = (kc[:, None, :] == qc.to(device)[:, :, None]) & (kc[:, None, :] >= 0)          # [B, heads, S]
+    P = match.to(F64) / match.sum(-1, keepdim=True).clamp_min(1).to(F64)
+    return (P @ c.k.to(device)).reshape(P.shape[0], -1), P
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# the committed cases: the GPU tests take their operands from here, the CPU test proves the claims for exactly these
+# ---------------------------------------------------------------------------------------------------------------------------------
+GEMM_SHAPES = {
+    128: [(1, 1, 1), (7, 5, 20), (129, 127, 65), (200, 130, 136), (128, 128, 192)],
+    256: [(256, 256, 64 * k) for k in range(1, 6)] + [(512, 768, 128)],
+    64: [(64, 64, 64), (128, 192, 640), (320, 64, 192)],
+}
+GEMM_PERSISTENT = (5120, 4096, 192)
+GEMM_SPLIT_K = 64 * 11
+GEMM_SLAB = (256, 256, 64 * 64)
+GEMM_EPILOGUE_SHAPE = {128: (200, 136, 136), 256: (256, 512, 256), 64: (128, 192, 256)}  # K >= 256 on the DMA tilings: bf16 outputs that round
+
+
+def gemm_seed(M, N, K):
+    return (M * 31 + N) * 17 + K
+
+
+_CASES = {}
+
+
+def attn(N, h, Lq, Lk, d, causal=False, mode="classes", lengths=None, v_bound=V_BOUND):
+    """The committed case of this geometry (built once per process and shared: treat it as read-only)."""
+    key = (N, h, Lq, Lk, d, causal, mode, None if lengths is None else tuple(lengths), v_bound)
+    if key not in _CASES:
+        seed = (((N * 7 + h) * 1009 + Lq) * 4099 + Lk) * 13 + d + (8 if causal else 0) + {"classes": 0, "class_const": 1, "uniform": 2}[mode]
+        _CASES[key] = attention_case(N, h, Lq, Lk, d, seed, lengths=lengths, causal=causal, mode=mode, v_bound=v_bound)
+    return _CASES[key]
+
+
+FUSED_D = (32, 64, 96, 160, 320, 480)
+FUSED_SHAPES = [(4, 2, 40, 72), (4, 3, 130, 292)]
+CAUSAL_SHAPE, CAUSAL_D = (4, 2, 70, 70), (32, 64, 96)
+FLASH_64 = (4, 3, 130, 520)
+RESIDENT_SELF = [(4, 2, 292, 292), (4, 2, 384, 384)]
+RESIDENT_CROSS = [(4, 2, 1, 384), (4, 2, 257, 292)]
+RESIDENT_MANY = (40, 8, 320, 320)
+SPLIT_KV = (4, 2, 40, 3840)
+DECODE = [(40, 8, 37), (300, 1, 129)]
+DECODE_APPEND, DECODE_APPEND_T = (40, 8, 37), (0, 17, 36)   # (N, h, cache length), the positions appended
+SCORES = [(d, Lk) for d in (128, 192, 320) for Lk in (8, 200, 376)]   # (head_dim, Lk) of the K17 cases; N 4, h 2, Lq 40
+UNFUSED = [(4, 2, 13, 200, 20, False), (4, 2, 5, 5, 4, True)]
+MQA = [(3, 1000), (7, 37), (1, 8200)]
+
+
+def decode_append_lengths(N, t):
+    """Valid prefixes for the decode step at position t: one item up to and including t, one cut short (position t is cached but not
+    attended: a PAD token), one with a single valid key, one with none."""
+    base = [t + 1, cut_length(t + 1), 1, 0]
+    return [base[i % 4] for i in range(N)]
+
+
+def all_attention_cases():
+    """Every (args, kwargs) the GPU tests pass to ``attn``."""
+    out = []
+    for d in FUSED_D:
+        for shape in FUSED_SHAPES:
+            out += [(shape + (d,), dict(mode=m)) for m in ("classes", "class_const", "uniform")]
+    out += [(CAUSAL_SHAPE + (d,), dict(causal=True, mode=m)) for d in CAUSAL_D for m in ("classes", "class_const")]
+    for shape in [FLASH_64] + RESIDENT_SELF + RESIDENT_CROSS + [SPLIT_KV]:
+        out += [(shape + (64,), dict(mode=m)) for m in ("classes", "class_const", "uniform")]
+    out += [(RESIDENT_MANY + (64,), dict(mode="class_const"))]
+    out += [((N, h, 1, Lk, 64), {}) for (N, h, Lk) in DECODE]
+    out += [(DECODE_APPEND[:2] + (1, DECODE_APPEND[2], 64), dict(lengths=decode_append_lengths(DECODE_APPEND[0], t))) for t in DECODE_APPEND_T]
+    out += [((4, 2, 40, Lk, d), dict(mode=m)) for (d, Lk) in SCORES for m in ("classes", "class_const", "uniform")]
+    for (N, h, Lq, Lk, d, causal) in UNFUSED:
+        out += [((N, h, Lq, Lk, d), dict(causal=causal, mode=m, v_bound=4 if m == "uniform" else V_BOUND))
+                for m in (("classes", "class_const") if causal else ("classes", "class_const", "uniform"))]
+    return out
+
