@@ -10,7 +10,10 @@ attention  the first C <= min(d, 8) head dimensions carry a class code: key j of
            -2^10 at every code dimension but c.  A score is 0 inside the class and -2^20 outside (exp of it, times any 1/sqrt(d), is 0 in
            f32), so the probabilities are exactly 1/n on the n valid keys of the class.  Class sizes are the powers of two of the binary
            decomposition of the valid length, scattered over the positions by a seeded permutation per (item, head).  V is integers in
-           [-127, 127]; O is the exact class mean."""
+           [-127, 127]; O is the exact class mean.
+K8         the same class code carried over to the co-attention's rank-1 score (see "K8" below): every entry of A and Bm^T is 1/n or 0,
+           and the kernels' bf16 roundings are restated at the points where they round (interaction_restated).
+K16        the encoder chain's parameters written so that each stage stands alone (see "K16" below): integers, signed permutations, zeros."""
 import torch
 
 F64 = torch.float64
@@ -372,3 +375,308 @@ def all_attention_cases():
                 for m in (("classes", "class_const") if causal else ("classes", "class_const", "uniform"))]
     return out
 
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# K8, the dual co-attention (csrc/interaction.hip): U[i, j] = w1 . Eq[j] + w2 . Ep[i] + (w3 o Ep[i]) . Eq[j]
+# ---------------------------------------------------------------------------------------------------------------------------------
+# A few "code" dimensions inside ONE 64-wide K group carry the class: passage row i of class c has 2^5 at code dimension c, query row j of
+# class c has -2^5 at every OTHER code dimension, and w3 = 2^10 there: the score is 0 inside the class and -2^20 outside.  w3 = 0 on every
+# other dimension, which holds the payload: integers in [-bound, bound].  w1 = -2^20 on one marker dimension that a few ("marked") query rows
+# carry as 1: those columns drop out of the softmax over j; w2 = -2^20 on another marker dimension that a few passage rows carry: those rows
+# drop out of the softmax over i.  (A marked passage row keeps its own softmax over j: its scores move together.)  The unmarked valid rows of
+# a class are a power of two, so every entry of A and Bm^T is exactly 1 / n or 0; w3 Eq + w2 is 0, -2^15 or -2^20: exact in bf16.
+K8_H, K8_LQ = 512, 64
+K8_CODE, K8_W3, K8_SOFT = 32.0, 1024.0, -2.0 ** 20
+K8_CODE_OFFSETS = (1, 9, 34, 43, 62)          # inside the K group: both lane halves, four different K steps
+K8_Q_PARTS, K8_Q_MARKED = (32, 16, 8), 4      # 56 unmarked valid query rows + 4 marked + 4 padded, scattered
+K8_P_PARTS = {32: (16, 8, 4), 96: (64, 16, 8), 384: (256, 64, 32), 416: (256, 128, 16), 512: (256, 128, 64)}
+K8_P_MARKED = {32: 2, 96: 4, 384: 8, 416: 8, 512: 8}
+
+
+def k8_dims(gk, ncode=3):
+    """(code dimensions, marker of w1, marker of w2): the code in K group gk, the markers three and five groups further."""
+    return [64 * gk + o for o in K8_CODE_OFFSETS[:ncode]], 64 * ((gk + 3) % 8) + 21, 64 * ((gk + 5) % 8) + 50
+
+
+def _k8_side(L, classes, parts, marked, g):
+    """(valid [L], class [L], marked [L]): the parts scattered over the L positions; marked and padded rows carry a class of the side too."""
+    perm = torch.randperm(L, generator=g)
+    cls = torch.tensor(classes)[torch.randint(0, len(classes), (L,), generator=g)]
+    valid, mark = torch.zeros(L, dtype=torch.bool), torch.zeros(L, dtype=torch.bool)
+    pos = 0
+    for c, n in zip(classes, parts):
+        cls[perm[pos:pos + n]] = c
+        valid[perm[pos:pos + n]] = True
+        pos += n
+    assert pos + marked <= L
+    valid[perm[pos:pos + marked]] = True
+    mark[perm[pos:pos + marked]] = True
+    return valid, cls, mark
+
+
+class InteractionCase(object):
+    """Eq [B, nq, 64, 512], Ep [B, P, Lp, 512] float64 (exact in bf16), qv [B, nq, 64], pv [B, P, Lp] bool, w [1, 1536] float64."""
+
+    def pairs(self, device="cpu"):
+        """The operands expanded per pair: Eq [n, 64, H], Ep [n, Lp, H], qv [n, 64], pv [n, Lp]."""
+        B, nq, P = self.B, self.nq, self.P
+        Eq = self.Eq.to(device).expand(B, P, K8_LQ, K8_H) if nq != P else self.Eq.to(device)
+        qv = self.qv.to(device).expand(B, P, K8_LQ) if nq != P else self.qv.to(device)
+        return (Eq.reshape(B * P, K8_LQ, K8_H), self.Ep.to(device).reshape(B * P, self.Lp, K8_H), qv.reshape(B * P, K8_LQ),
+                self.pv.to(device).reshape(B * P, self.Lp))
+
+
+def interaction_case(B, P, nq, Lp, seed, gk=0, v_bound=V_BOUND, q=None, p=None):
+    """``q`` / ``p``: (classes, parts, marked) of the ordinary queries / passages (default: three classes on both sides).  Passage P - 1 of
+    sample 0 has two valid rows (classes 0 and 1), the first query of the last sample has no valid token (B > 1)."""
+    g = _gen(seed)
+    q = ((0, 1, 2), K8_Q_PARTS, K8_Q_MARKED) if q is None else q
+    p = ((0, 1, 2), K8_P_PARTS[Lp], K8_P_MARKED[Lp]) if p is None else p
+    ncode = 1 + max(max(q[0]), max(p[0]))
+    code, m1, m2 = k8_dims(gk, ncode)
+    code_t = torch.tensor(code)
+    c = InteractionCase()
+    c.B, c.P, c.nq, c.Lp, c.gk, c.v_bound, c.code, c.m1, c.m2 = B, P, nq, Lp, gk, v_bound, code, m1, m2
+    c.Eq = ints((B, nq, K8_LQ, K8_H), seed + 7919, bound=v_bound)
+    c.Ep = ints((B, P, Lp, K8_H), seed + 104729, bound=v_bound)
+    c.qv, c.pv = torch.zeros(B, nq, K8_LQ, dtype=torch.bool), torch.zeros(B, P, Lp, dtype=torch.bool)
+    c.q_marked, c.p_marked = torch.zeros_like(c.qv), torch.zeros_like(c.pv)
+    for b in range(B):
+        for k in range(nq):
+            valid, cls, mark = _k8_side(K8_LQ, q[0], q[1], q[2], g)
+            if B > 1 and b == B - 1 and k == 0:
+                valid = torch.zeros_like(valid)  # codes, markers and payload stay: only the mask says that these rows do not count
+            c.Eq[b, k][:, code_t] = torch.where(cls[:, None] == torch.arange(ncode)[None, :], 0.0, -K8_CODE).to(F64)
+            c.Eq[b, k][:, m1] = mark.to(F64)
+            c.qv[b, k], c.q_marked[b, k] = valid, mark & valid
+        for k in range(P):
+            side = ((0, 1), (1, 1), 0) if (b == 0 and k == P - 1) else p
+            valid, cls, mark = _k8_side(Lp, side[0], side[1], side[2], g)
+            c.Ep[b, k][:, code_t] = torch.where(cls[:, None] == torch.arange(ncode)[None, :], K8_CODE, 0.0).to(F64)
+            c.Ep[b, k][:, m2] = mark.to(F64)
+            c.pv[b, k], c.p_marked[b, k] = valid, mark
+    w = torch.zeros(3 * K8_H, dtype=F64)
+    w[m1], w[K8_H + m2] = K8_SOFT, K8_SOFT
+    w[2 * K8_H + code_t] = K8_W3
+    c.w = w.reshape(1, 3 * K8_H)
+    return c
+
+
+def bf16_f64(x):
+    """float64 -> f32 -> bf16 (each to nearest even) -> float64: a bf16 store of an f32 value, restated."""
+    return x.to(torch.float32).to(torch.bfloat16).to(F64)
+
+
+def interaction_restated(Eq, Ep, qv, pv, w):
+    """The kernels' arithmetic in float64 with their bf16 roundings at the points where they round (operands per pair, any device):
+    w3 Eq + w2 once in LDS; A and Bm^T as stored; A1 = A Eq and B1 = Bm^T Ep once (tile_to_lds) -- A2 = A B1, B2 = Bm^T A1 and the four
+    elementwise products (mul8) read the ROUNDED values.  Returns the stored values ("A", "Bt", "Gqp", "Gpq": float64 holding bf16 values,
+    padded rows 0) and, under "raw", the values in front of each rounding (what must be exact in f32 for the exact cases)."""
+    H = K8_H
+    w1, w2, w3 = w.reshape(-1)[:H], w.reshape(-1)[H:2 * H], w.reshape(-1)[2 * H:]
+    bq = bf16_f64(Eq * w3 + w2)
+    U = (Eq @ w1)[:, None, :] + Ep @ bq.transpose(1, 2)                                    # [n, Lp, 64]
+    mask = pv[:, :, None] & qv[:, None, :]
+    U = torch.where(mask, U, torch.full_like(U, float("-inf")))
+
+    def softmax(u, dim):
+        m = u.max(dim, keepdim=True).values
+        e = torch.where(mask, torch.exp(u - torch.where(torch.isinf(m), torch.zeros_like(m), m)), torch.zeros_like(u))
+        s = e.sum(dim, keepdim=True)
+        return e / torch.where(s > 0, s, torch.ones_like(s))
+
+    raw = {"U": U, "A": softmax(U, 2), "Bt": softmax(U, 1).transpose(1, 2)}
+    A, Bt = bf16_f64(raw["A"]), bf16_f64(raw["Bt"])
+    raw["A1"], raw["B1"] = A @ Eq + 0.0, Bt @ Ep + 0.0                                     # (+ 0.0: a sum of -0 terms is +0 on the MFMA)
+    A1, B1 = bf16_f64(raw["A1"]), bf16_f64(raw["B1"])
+    raw["A2"], raw["B2"] = A @ B1 + 0.0, Bt @ A1 + 0.0
+    A2, B2 = bf16_f64(raw["A2"]), bf16_f64(raw["B2"])
+    raw["EpA1"], raw["EpA2"], raw["EqB1"], raw["EqB2"] = Ep * A1, Ep * A2, Eq * B1, Eq * B2
+    zero = torch.zeros((), dtype=F64, device=Eq.device)
+    Gqp = torch.where(pv[:, :, None], torch.cat([Ep, A1, A2, bf16_f64(raw["EpA1"]), bf16_f64(raw["EpA2"])], -1), zero)
+    Gpq = torch.where(qv[:, :, None], torch.cat([Eq, B1, B2, bf16_f64(raw["EqB1"]), bf16_f64(raw["EqB2"])], -1), zero)
+    return {"A": A, "Bt": Bt, "Gqp": Gqp, "Gpq": Gpq, "raw": raw}
+
+
+K8_GEOMETRY = [(3, 3, nq, Lp) for Lp in (32, 96, 384, 416, 512) for nq in (1, 3)]   # (B, P, nq, Lp): nq = 1 is eq_div = P
+K8_GROUPS = (3, 3, 1, 96)                                                          # the shape of the eight K-group cases
+K8_SMALL_PAYLOAD = [(3, 3, 1, 384), (3, 3, 3, 96)]                                  # |v| <= 15
+K8_MANY = (29, 9, 1, 32)                                                           # 261 pairs: more than the 256 CUs
+K8_ORPHAN = (3, 3, 1, 96)  # query class 4 and passage class 3 have no counterpart: uniform over ALL unmarked valid rows (32 and 64 of them)
+K8_ORPHAN_Q, K8_ORPHAN_P = ((0, 1, 2, 4), (16, 8, 4, 4), 4), ((0, 1, 2, 3), (32, 16, 8, 8), 4)
+
+_K8 = {}
+
+
+def k8(B, P, nq, Lp, gk=None, v_bound=V_BOUND, orphan=False):
+    """The committed K8 case (built once per process: read-only).  gk None: the K group follows from the geometry."""
+    gk = (Lp // 32 + nq) % 8 if gk is None else gk
+    key = (B, P, nq, Lp, gk, v_bound, orphan)
+    if key not in _K8:
+        seed = ((((B * 31 + P) * 7 + nq) * 1031 + Lp) * 11 + gk) * 3 + (1 if v_bound == V_BOUND else 0) + (500000 if orphan else 0)
+        _K8[key] = interaction_case(B, P, nq, Lp, seed, gk=gk, v_bound=v_bound, q=K8_ORPHAN_Q if orphan else None,
+                                    p=K8_ORPHAN_P if orphan else None)
+    return _K8[key]
+
+
+def all_k8_cases():
+    """Every (args, kwargs) the GPU tests pass to ``k8``."""
+    out = [(s, {}) for s in K8_GEOMETRY]
+    out += [(K8_GROUPS, dict(gk=gk)) for gk in range(8)]
+    out += [(s, dict(v_bound=GEMM_BOUND)) for s in K8_SMALL_PAYLOAD]
+    out += [(K8_MANY, {}), (K8_ORPHAN, dict(orphan=True))]
+    return out
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# K16, the encoder chain (csrc/encoder_chain.hip): y = ctx Wo^T + bo + s; s2 = LN2(y); a = gelu(s2 W1^T + b1); o = a W2^T + b2 + s2;
+# s' = LN1'(o); qkv' = s' Wqkv'^T + bqkv'.  The layer's parameters are written so that each stage stands alone.
+# ---------------------------------------------------------------------------------------------------------------------------------
+CHAIN_E = 512
+CHAIN_EPS2, CHAIN_EPS1N = 0.5, 2.0   # clearly different: on the quiet rows (variance 1 to 3) swapping them moves the result by tens of bf16 steps
+CHAIN_M = (1, 15, 16, 17, 63, 64, 65, 127, 128, 129, 191, 257)
+CHAIN_GAMMA = (0.0, 0.5, -0.5, 1.0, -1.0, 1.5, 2.0, -0.25)
+CHAIN_BETA = (0.0, 0.25, -0.25, 1.0, -1.0, 3.0, 0.0, 0.5)
+CHAIN_PERMS = (0, 5, 11)
+
+
+def pick(n, seed, values):
+    return torch.tensor(values, dtype=F64)[torch.randint(0, len(values), (n,), generator=_gen(seed))]
+
+
+def chain_tokens(M, seed, quiet="small", bound=GEMM_BOUND):
+    """[M, 512] integers in [-bound, bound], a different row per token; every third row is "quiet": integers in [-1, 1] ("small") or 0."""
+    x = ints((M, CHAIN_E), seed, bound=bound)
+    q = torch.arange(M) % 3 == 1
+    small = ints((M, CHAIN_E), seed + 1, bound=1, zero_share=0.0) if quiet == "small" else torch.zeros(M, CHAIN_E, dtype=F64)
+    return torch.where(q[:, None], small, x)
+
+
+def signed_perm(r, seed, blocks=1):
+    """[512 blocks, 512]: per block of 512 rows a signed permutation times a power of two (2^-1 .. 2^2).  Row n = 16 fb + i of block c has
+    its one entry in column 32 ((i + fb + r + c) % 16) + (fb + 3 (r + c)) % 32: every (16 features x 32 k) fragment of the weight pack
+    holds exactly one non-zero entry."""
+    g = _gen(seed)
+    out = []
+    for c in range(blocks):
+        n = torch.arange(CHAIN_E)
+        fb, i = n // 16, n % 16
+        col = 32 * ((i + fb + r + c) % 16) + (fb + 3 * (r + c)) % 32
+        val = (torch.randint(0, 2, (CHAIN_E,), generator=g) * 2 - 1).to(F64) * 2.0 ** torch.randint(-1, 3, (CHAIN_E,), generator=g).to(F64)
+        w = torch.zeros(CHAIN_E, CHAIN_E, dtype=F64)
+        w[n, col] = val
+        out.append(w)
+    return torch.cat(out, 0)
+
+
+GELU_TARGETS = tuple(range(8, 65)) + tuple(range(-64, -19)) + (0,) * 40   # pre-activations of which gelu_f gives exactly x, -0 or 0
+
+
+def chain_layer(kind, seed=0):
+    """The layer's tensors as float64 (all exact in bf16 / f32).  kind:
+    "A"  W1 = 0, b1 = b2 = 0 (a = gelu(0) = 0, o = s2): dense integer Wo, bo in [-2, 2], dyadic g2 / be2 with zeros and negative entries;
+    "Ap" as A with Wo a signed permutation;
+    "B1" g2 = 0 (s2 = be2 on every token), integer be2 / W1 and b1 such that every pre-activation is a GELU_TARGET; dense integer W2, b2 = 0;
+    "B3" as B1 with W1 a signed permutation and b2 != 0;
+    "B2" be2 = 0, W1 = 0, b1 a dyadic grid over [-8, 8), W2 a signed permutation, b2 = 0: o[n] = +-2^k bf16(gelu(b1[pi(n)]))."""
+    E, z = CHAIN_E, torch.zeros(CHAIN_E, dtype=F64)
+    lay = {"kind": kind, "eps2": CHAIN_EPS2}
+    lay["Wo"] = signed_perm(3, seed + 1) if kind == "Ap" else ints((E, E), seed + 1)
+    lay["bo"] = ints((E,), seed + 2, bound=2)
+    if kind in ("A", "Ap"):
+        lay["g2"], lay["be2"] = pick(E, seed + 3, CHAIN_GAMMA), pick(E, seed + 4, CHAIN_BETA)
+        lay["W1"], lay["b1"], lay["W2"], lay["b2"] = torch.zeros(E, E, dtype=F64), z, ints((E, E), seed + 5), z
+    elif kind in ("B1", "B3"):
+        lay["g2"], lay["be2"] = z, ints((E,), seed + 4, bound=3)
+        lay["W1"] = signed_perm(7, seed + 6) if kind == "B3" else ints((E, E), seed + 6)
+        lay["target"] = pick(E, seed + 7, GELU_TARGETS)
+        lay["b1"] = lay["target"] - lay["W1"] @ lay["be2"]
+        lay["W2"], lay["b2"] = ints((E, E), seed + 5), (ints((E,), seed + 8) if kind == "B3" else z)
+    else:
+        assert kind == "B2"
+        lay["g2"], lay["be2"], lay["W1"] = z, z, torch.zeros(E, E, dtype=F64)
+        lay["b1"] = (torch.arange(E, dtype=F64) / 32.0 - 8.0)[torch.randperm(E, generator=_gen(seed + 9))]
+        lay["W2"], lay["b2"] = signed_perm(2, seed + 10), z
+    return lay
+
+
+def chain_next(r, seed=0):
+    """The next layer's norm1 and in-projection: dyadic g1n / be1n; Wqkv three signed permutations (r in CHAIN_PERMS) or dense integers
+    (r None); bqkv multiples of 1/4 in [-2, 2]."""
+    nxt = {"r": r, "eps1n": CHAIN_EPS1N, "g1n": pick(CHAIN_E, seed + 21, CHAIN_GAMMA), "be1n": pick(CHAIN_E, seed + 22, CHAIN_BETA)}
+    nxt["Wqkv"] = ints((3 * CHAIN_E, CHAIN_E), seed + 23) if r is None else signed_perm(r, seed + 23, blocks=3)
+    nxt["bqkv"] = ints((3 * CHAIN_E,), seed + 24, bound=8) / 4.0
+    return nxt
+
+
+def layer_norm64(y, gamma, beta, eps):
+    """(LN(y), xhat) in float64 (biased variance, as nn.LayerNorm)."""
+    mean = y.mean(-1, keepdim=True)
+    var = ((y - mean) ** 2).mean(-1, keepdim=True)
+    xhat = (y - mean) / torch.sqrt(var + eps)
+    return xhat * gamma + beta, xhat
+
+
+def layer_norm_bound(ref, xhat, gamma, beta):
+    """One bf16 step at a tie plus the f32 evaluation error on the terms in front of their cancellation."""
+    return 2.0 ** -8 * ref.abs() + 2.0 ** -20 * ((xhat * gamma).abs() + beta.abs())
+
+
+def layer_norm_f32(y, gamma, beta, eps, order_seed, two_pass=False):
+    """The kernel's f32 LayerNorm restated on the CPU with a shuffled sum: one pass (E[x^2] - mean^2, stages 0 and 2) or two (the head)."""
+    x = y.to(torch.float32)
+    perm = torch.randperm(x.shape[-1], generator=_gen(order_seed))
+    inv = torch.tensor(1.0 / CHAIN_E, dtype=torch.float32)
+
+    def total(t):
+        acc = torch.zeros(t.shape[:-1], dtype=torch.float32)
+        for idx in perm.chunk(8):
+            acc = acc + t[..., idx].sum(-1)
+        return acc
+
+    mean = total(x) * inv
+    if two_pass:
+        var = total((x - mean[..., None]) ** 2) * inv
+    else:
+        var = (total(x * x) * inv - mean * mean).clamp_min(0.0)
+    rstd = torch.rsqrt(var + torch.tensor(eps, dtype=torch.float32))
+    return ((x - mean[..., None]) * rstd[..., None]) * gamma.to(torch.float32) + beta.to(torch.float32)
+
+
+def chain_y(ctx, s, lay):
+    dev = ctx.device
+    return ctx @ lay["Wo"].to(dev).t() + lay["bo"].to(dev) + s
+
+
+def gelu64(x):
+    return 0.5 * x * (1.0 + torch.erf(x / 2.0 ** 0.5))
+
+
+def gelu_f32(x):
+    """common.h's gelu_terms / gelu_f restated in f32 on the CPU (separate multiplies and adds where the kernel has FMAs) -> (gelu, Phi)."""
+    f = lambda v: torch.tensor(v, dtype=torch.float32)
+    x = x.to(torch.float32)
+    z = x.abs() * f(0.70710678118654752)
+    t = 1.0 / (f(0.3275911) * z + 1.0)
+    e = torch.exp(-z * z)
+    p = f(1.061405429) * t + f(-1.453152027)
+    for c in (1.421413741, -0.284496736, 0.254829592):
+        p = p * t + f(c)
+    q = 0.5 * p * t * e
+    cdf = torch.where(x >= 0, 1.0 - q, q)
+    return x * cdf, cdf
+
+
+def gelu_eps_phi(grid):
+    """max |Phi_f32(x) - Phi_64(x)| over the grid, DOUBLED for the device's v_rcp and v_exp: the Phi term of the GELU bar."""
+    phi64 = 0.5 * (1.0 + torch.erf(grid.to(F64) / 2.0 ** 0.5))
+    return 2.0 * (gelu_f32(grid)[1].to(F64) - phi64).abs().max().item()
+
+
+def chain_ffn(lay, rows=1):
+    """Families B1 / B3: (s2, a, o) of one token in float64 -- the same for every token, since g2 = 0."""
+    s2 = lay["be2"]
+    pre = lay["W1"] @ s2 + lay["b1"]
+    a = torch.where(pre > 0, pre, torch.zeros_like(pre))
+    return s2, a, lay["W2"] @ a + lay["b2"] + s2

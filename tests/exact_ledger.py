@@ -1,5 +1,6 @@
-"""Bookkeeping of the exact-arithmetic GPU tests (test_gemm_exact_gpu.py, test_attention_exact_gpu.py): per test function the C entry
-points that ran, the cases, and the number of elements compared exactly and by a bound.  It is what profiles/exact_parity.json is made from;
+"""Bookkeeping of the exact-arithmetic GPU tests (test_gemm_exact_gpu.py, test_attention_exact_gpu.py, test_interaction_exact_gpu.py,
+test_encoder_chain_exact_gpu.py): per test function the C entry points that ran, the cases, and the number of elements compared exactly and
+by a bound.  It is what profiles/exact_parity.json and profiles/fused_exact_parity.json are made from;
 no assertion depends on it.  Nothing is written unless CASE_EXACT_LEDGER names a file."""
 import pytest
 
@@ -29,6 +30,13 @@ def record(exact, bounded=0, reason=None):
     cur["bounded"] += int(bounded)
     if bounded and reason and reason not in cur["bound_reasons"]:
         cur["bound_reasons"].append(reason)
+
+
+def note(key, value):
+    """A measured figure of the current test (LayerNorm flip shares, eps_phi, per-segment errors), kept under "figures"."""
+    cur = _CURRENT[0]
+    if cur is not None:
+        cur.setdefault("figures", {})[key] = value
 
 
 def _dump():
