@@ -15,6 +15,7 @@ from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, Transforme
 from ..common.Utils import to_sentence, token_freq_table
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
 from ..evaluation.attribution import attribute_answers
+from ..evaluation.risk import MRT_DEFAULTS, minimum_risk_step
 from ..evaluation.rouge_ids import consensus_answers
 
 
@@ -54,10 +55,10 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
-                score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None):
+                score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
                          score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram,
-                         decode_rules=decode_rules, segments=segments)
+                         decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
 
 
 class RelevantPassageSelection(nn.Module):
@@ -141,7 +142,7 @@ class ResponseGeneration(nn.Module):
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
                span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0,
-               decode_rules=None, segments=None):
+               decode_rules=None, segments=None, score_grad_head=False):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -155,7 +156,7 @@ class ResponseGeneration(nn.Module):
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
 
 
 class CaSE(nn.Module):
@@ -189,6 +190,7 @@ class CaSE(nn.Module):
         self.min_length = 0
         self.banned_ids = None
         self.length_penalty = 1.0
+        self.mrt = dict(MRT_DEFAULTS)  # do_mrt's defaults (evaluation.risk): num_samples, alpha, with_reference, dedup, mle_weight, temperature, top_k, top_p
         self.support_top_k = 32  # do_extract's default K: this many supporting tokens per item
         # the per-id frequency table of the token supervision (K37), installed by set_token_freq: it moves with .to() and is no state_dict key
         self.register_buffer("token_freq", None, persistent=False)
@@ -244,18 +246,45 @@ class CaSE(nn.Module):
             return data['token_label'], data['token_weight']
         return self._token_labels(data, who="do_train")
 
-    def do_train(self, data):
-        token_label, token_weight = self._token_supervision(data)
-        eq, ep, ps, se = self._encode_select_extract(data)
+    @staticmethod
+    def _stage_losses(data, ps, se, token_label, token_weight):
+        """The passage-selection and token-identification losses of a training batch, from the stages' outputs: what ``do_train`` and
+        ``do_mrt`` share."""
         loss_ps = passage_bce(ps[0], data['passage_label'])
         valid = data['passage'].ne(0).float()
         bce = torch.nn.functional.binary_cross_entropy_with_logits(se[0], token_label.detach(), reduction='none')
         loss_se = (valid * bce * token_weight.detach()).sum() / valid.sum()
+        return [loss_ps, loss_se]
+
+    def do_train(self, data):
+        token_label, token_weight = self._token_supervision(data)
+        eq, ep, ps, se = self._encode_select_extract(data)
+        loss_ps, loss_se = self._stage_losses(data, ps, se, token_label, token_weight)
         rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
                                              encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
                                              output=data['response'])
         dist1, dist2 = rg[2]
         return [loss_ps, loss_se, generation_nll(ops.add(dist1, dist2), data['response'])]
+
+    def do_mrt(self, data, candidates=None, num_samples=None, alpha=None, with_reference=None, dedup=None, mle_weight=None, details=False,
+               **sampling):
+        """Minimum-risk training on ROUGE-L (``evaluation.risk``): the expected  1 - ROUGE-L F  of a pool of candidates under the model's
+        renormalised posterior  Q_n ~ p(candidate n)^alpha,  instead of the token-level NLL of ``do_train``.  The pool is ``num_samples``
+        draws of ``do_sample`` (``**sampling``: ``temperature`` / ``top_k`` / ``top_p`` / ``uniforms`` / ``no_repeat_ngram`` / ``min_length`` /
+        ``banned_ids``; drawn under no_grad from the global counter stream) or explicit ``candidates`` int64 [B, N, T]; with ``with_reference``
+        ``data['response']`` joins as the last candidate; with ``dedup`` a candidate that repeats an earlier one is left out of the
+        posterior.  The pool is scored teacher-forced with grad (K29 with row statistics and K41 where the build has them, the unfused
+        chain otherwise).  ``mle_weight`` adds that multiple of the reference's NLL (``do_score``'s ``loss``; needs the reference).  None
+        takes the value from ``self.mrt``.  At most 64 candidates (the reference included) of at most 256 positions.
+        -> the list ``do_train`` returns with the generation loss replaced by  mean risk + mle_weight x nll_ref;  ``details=True``: a dict
+        with that list under ``losses`` plus ``risk`` [B], ``q`` [B, N], ``cost`` [B, N], ``valid`` [B, N], ``candidates`` [B, N, T] (the pool
+        as scored) and ``token_probs`` [B, N, T].  LIMIT: an MRT step runs WITHOUT DROPOUT -- the module is switched to eval mode (grad
+        enabled) for the call and its previous mode is restored afterwards, also after an exception -- so a trainer that called
+        ``model.train()`` drives it unchanged.  Nothing is read back."""
+        token_label, token_weight = self._token_supervision(data)
+        return minimum_risk_step(self, data, lambda: self._encode_select_extract(data),
+                                 lambda enc: self._stage_losses(data, enc[2], enc[3], token_label, token_weight), candidates, num_samples, alpha,
+                                 with_reference, dedup, mle_weight, details, **sampling)
 
     def _respond(self, data, _enc=None, **mode):
         """Encode, select, extract, then the decoder in the mode the keyword names: (the decoder's raw result, rank)."""
@@ -418,6 +447,8 @@ class CaSE(nn.Module):
         # the ids themselves feed the pointer scatter kernel instead
         if method == 'train':
             return self.do_train(data)
+        elif method == 'mrt_train':
+            return self.do_mrt(data)
         elif method == 'test':
             return self.do_test(data)
         elif method == 'beam':

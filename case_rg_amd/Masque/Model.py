@@ -10,6 +10,7 @@ from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, Transforme
 from ..common.Utils import to_sentence
 from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair
 from ..evaluation.attribution import attribute_answers
+from ..evaluation.risk import MRT_DEFAULTS, minimum_risk_step
 from ..evaluation.rouge_ids import consensus_answers
 
 
@@ -37,9 +38,9 @@ class MasqueTransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0, decode_rules=None, segments=None):
+                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
 
 
 class PassageSelection(nn.Module):
@@ -85,7 +86,8 @@ class ResponseGeneration(nn.Module):
         self.decoder = decoder
 
     def action(self, query, passage, source_map, encode_query=None, encode_passage=None, passage_selection_result=None,
-               output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None):
+               output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None,
+               score_grad_head=False):
         if encode_query is None:
             encode_query = self.query_encoder(query)[0][:, :, -1]
         if encode_passage is None:
@@ -100,7 +102,7 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep, passage_rep], self.BOS, self.UNK, source_map, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
 
 
 class Masque(nn.Module):
@@ -131,6 +133,7 @@ class Masque(nn.Module):
         self.min_length = 0
         self.banned_ids = None
         self.length_penalty = 1.0
+        self.mrt = dict(MRT_DEFAULTS)  # do_mrt's defaults (evaluation.risk): num_samples, alpha, with_reference, dedup, mle_weight, temperature, top_k, top_p
         self.response_generation.decoder.beam_eos_id = vocab2id[EOS_WORD]
         if early_stop:  # greedy decoding ends once every answer of the batch has produced EOS (off = the reference's fixed T steps)
             self.response_generation.decoder.eos_id = vocab2id[EOS_WORD]
@@ -151,7 +154,21 @@ class Masque(nn.Module):
         eq, ep, ps = self._encode_select(data)
         rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
                                              encode_passage=ep, passage_selection_result=ps, output=data['response'])
-        return [0.25 * passage_bce(ps[0], data['passage_label']), generation_nll(rg[2], data['response'])]
+        return self._stage_losses(data, ps) + [generation_nll(rg[2], data['response'])]
+
+    @staticmethod
+    def _stage_losses(data, ps):
+        """The passage-selection loss of a training batch, from the stage's output: what ``do_train`` and ``do_mrt`` share."""
+        return [0.25 * passage_bce(ps[0], data['passage_label'])]
+
+    def do_mrt(self, data, candidates=None, num_samples=None, alpha=None, with_reference=None, dedup=None, mle_weight=None, details=False,
+               **sampling):
+        """Minimum-risk training on ROUGE-L over a sampled pool or explicit ``candidates`` (see CaSE.do_mrt and ``evaluation.risk``): the list
+        ``do_train`` returns with the generation loss replaced by  mean risk + mle_weight x nll_ref;  ``details=True``: a dict with that list
+        under ``losses`` plus ``risk``, ``q``, ``cost``, ``valid``, ``candidates`` and ``token_probs``.  The step runs without dropout: the module
+        is in eval mode for the call and its previous mode is restored afterwards."""
+        return minimum_risk_step(self, data, lambda: self._encode_select(data), lambda enc: self._stage_losses(data, enc[2]), candidates,
+                                 num_samples, alpha, with_reference, dedup, mle_weight, details, **sampling)
 
     def do_ps_train(self, data):
         _, _, ps = self._encode_select(data)
@@ -267,6 +284,8 @@ class Masque(nn.Module):
             return self.do_train(data)
         elif method == 'ps_train':
             return self.do_ps_train(data)
+        elif method == 'mrt_train':
+            return self.do_mrt(data)
         elif method == 'test':
             return self.do_test(data)
         elif method == 'beam':

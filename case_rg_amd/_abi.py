@@ -19,7 +19,7 @@ WS_ATTENTION_SPLITKV, WS_ATTENTION_BWD, WS_OPTIM_SUMSQ, WS_ENCODER_CHAIN_PACK, W
  FEAT_GEMM_DW_SLABS, FEAT_DECODER_CHAIN, FEAT_ATTN_DECODE_MQA, FEAT_POINTER_DECODE, FEAT_POINTER_HEAD, FEAT_GEMM_LN, FEAT_STEP_STATE,
  FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS, FEAT_NGRAM_BAN,
  FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS, FEAT_POINTER_HEAD_WIDE, FEAT_DECODE_RULES, FEAT_TOKEN_LABELS,
- FEAT_COPY_ATTRIBUTION, FEAT_METEOR) = (1 << i for i in range(30))
+ FEAT_COPY_ATTRIBUTION, FEAT_METEOR, FEAT_RISK_TRAIN) = (1 << i for i in range(31))
 EPI_BIAS_COL, EPI_BIAS_ROW, EPI_GELU, EPI_RELU = 1, 2, 4, 8
 EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ATOMIC, EPI_DROPOUT = 16, 32, 64, 128, 256
 
@@ -164,6 +164,9 @@ SIGNATURES = {
     "case_token_select": [ptr] * 7 + [i64, i64, i32, ptr],
     "case_copy_attribution": [ptr, ptr, i64, ptr, ptr, i32, ptr, i64, ptr, ptr, i32, ptr, ptr, ptr, ptr, i64, i64, i64, ptr],
     "case_meteor": [ptr] * 5 + [i64, f64, f64, f64] + [ptr] * 5 + [i64, i64, i64, i64, i64, ptr],
+    "case_pointer_head_score_stats": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64, ptr, ptr, ptr, i64, i64, i64, ptr],
+    "case_pointer_head_score_bwd": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64] + [ptr] * 6 + [i64, i64, i64, ptr],
+    "case_sequence_risk": [ptr] * 4 + [f64] + [ptr] * 3 + [i64, i64, i64, ptr],
     "case_gemm_ln": [C.POINTER(GemmDesc), ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, ptr, ptr],
     "case_optim_sumsq": [ptr, ptr, i64, ptr, ptr, ptr],
     "case_optim_adam_ema": [ptr, ptr, i64, ptr, f32, f64, f64, f64, f64, ptr, ptr],

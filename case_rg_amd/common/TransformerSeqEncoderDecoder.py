@@ -532,14 +532,16 @@ class PointerDecoderCore(nn.Module):
         setattr(self, mode.counter, steps)
         return mode.result(dec_out)
 
-    def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None, segments=None):
+    def _score(self, mems, valid, weights, source_map, BOS, answers, pad=0, feature_of=None, segments=None, grad_head=False):
         """Teacher-forced scoring of given answers (eval mode): ``answers`` int64 [B, T'] or [B, N, T'], ``pad`` marking the positions that
         are not scored.  One full-prefix pass over dec_ids = cat[BOS, answers[:, :-1]] (``_run_prefix``, causal), then the head over row
         chunks of at most ``score_chunk_rows`` (candidate, position) rows.  The N candidates of an item are extra batch rows (``_per_item``).
         The sorted source keys are NOT repeated: the rows of an item are consecutive and K29 reads key row r // rows_per_source.
         Under no_grad (and unless CASE_POINTER_SCORE=off) a chunk's head is ``_head_logits`` + K29 (ops.pointer_head_score): one read of the
         logits, no [rows, V] distribution.  With grad enabled it is the unfused differentiable chain of the training branch (``_generate``,
-        ``_mix``, a gather), so gradients reach the parameters.  Nothing is read back: the pass captures into one graph.
+        ``_mix``, a gather), so gradients reach the parameters.  ``grad_head`` (only ``do_mrt`` sets it): with grad enabled and where
+        ``ops.pointer_score_grad_supported``, a chunk's head is ``_head_logits`` + K29 with row statistics and K41 in the backward pass
+        (ops.pointer_head_score_grad) instead of the chain.  Nothing is read back: the pass captures into one graph.
         -> dict(token_probs [B, N, T'] (1 where PAD), copy_probs [B, N, T'] (the pointer part, 0 where PAD), scores [B, N] (mean over the
         scored targets of -log max(p, 1e-30)), loss [1] (sum of -log(p + 1e-8) over the scored targets / their count), tokens int64 scalar).
         ``segments`` (the G + 1 boundaries of ``evaluation.attribution.source_segments``; None: the launches of a pass without it): every
@@ -570,6 +572,9 @@ class PointerDecoderCore(nn.Module):
         flat = tgt.reshape(rows)
         sorted_src = isinstance(source_map, ops.SortedSource)
         fused = sorted_src and ops.pointer_score_supported(source_map, len(mems))
+        # the differentiable fused head (K29 with row statistics, K41 in the backward pass): only for a caller that asks (minimum-risk training)
+        fused_grad = bool(grad_head) and not fused and torch.is_grad_enabled() and ops.pointer_score_grad_supported(source_map, len(mems))
+        head_score = ops.pointer_head_score_grad if fused_grad else ops.pointer_head_score
         limit = max(1, int(self.score_chunk_rows))
         if per <= limit:  # whole items per chunk
             step = limit // per * per
@@ -585,9 +590,9 @@ class PointerDecoderCore(nn.Module):
             dec_out, gen_in = self._head_parts(dec_in[r0:r1], x[r0:r1], None if feat is None else feat[r0:r1])
             cx, cp, y = [c[r0:r1] for c in ctxs], [c[r0:r1] for c in copies], flat[r0:r1]
             b0, b1 = r0 // per, (r1 + per - 1) // per
-            if fused:  # K29: (max, sum) over the logits row, logit[y], and the pointer mass of y's run in the item's sorted keys
-                logits, mix_logits = self._head_logits(dec_out, gen_in, cx)
-                p, c = ops.pointer_head_score(logits, mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, pad)
+            if fused or fused_grad:  # K29: (max, sum) over the logits row, logit[y], and the pointer mass of y's run in the item's sorted keys
+                logits, mix_logits = self._head_logits(dec_out, gen_in, cx, with_grad=fused_grad)
+                p, c = head_score(logits, mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, pad)
                 if segments is not None and kernel:  # K39: the same run of the same keys, kept apart by segment
                     parts.append(ops.copy_attribution(mix_logits, source_map.select(slice(b0, b1)), n // (b1 - b0), cp, y, segments, pad))
                 elif segments is not None:
@@ -623,7 +628,7 @@ class PointerDecoderCore(nn.Module):
         return out
 
     def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None, segments=None):
+             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
         """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
         (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) and ``decode_rules`` (what ``decode_rules_param`` returned: min_length,
         banned ids, the beam length penalty) apply to the three decoding modes only."""
@@ -633,7 +638,7 @@ class PointerDecoderCore(nn.Module):
         valid = [m.reshape(B, -1).contiguous() for m in encode_masks]
         weights = None if encode_weights is None else [w.reshape(B, -1) for w in encode_weights]
         if score_index is not None:
-            return self._score(mems, valid, weights, source_map, BOS, score_index, feature_of=feature_of, segments=segments)
+            return self._score(mems, valid, weights, source_map, BOS, score_index, feature_of=feature_of, segments=segments, grad_head=score_grad_head)
         T = groundtruth_index.size(1) if max_target_length is None else max_target_length
         if self.training and groundtruth_index is not None:
             dec_ids = torch.cat([self._bos(B, BOS, dev), groundtruth_index[:, :-1]], dim=-1)
@@ -671,13 +676,17 @@ class PointerDecoderCore(nn.Module):
         # beam search repeats its rows at width 1 too
         return self._decode(mode, *self._per_item(n, mems, valid, weights, source_map, feat, unit_too=bool(beam_width)), BOS, T)
 
-    def _head_logits(self, dec_out, gen_in, ctxs):
-        """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 / K28 / K29 take."""
+    def _head_logits(self, dec_out, gen_in, ctxs, with_grad=False):
+        """The vocabulary logits and the mixing logits of one cached step (f32): what K23 / K24 / K28 / K29 take.  ``with_grad``: the
+        differentiated scoring pass of minimum-risk training -- the same launches with autograd behind them, so its probabilities carry the
+        bits of the no_grad pass."""
         B, V = dec_out.shape[0], self.tgt_vocab_size
         h = ops.linear(gen_in, self.gen[0].weight, self.gen[0].bias)
         logits = ops.linear(h, self.gen[-2].weight, None, out_dtype=torch.float32)
         parts = [dec_out] + ctxs
-        if ops.linear_skinny_supported(parts, self.mix.weight):  # the 1 + nmem mixing logits straight from the three inputs: no concatenation, no N = 3 GEMM tile
+        if with_grad and ops.linear_skinny_supported(parts, self.mix.weight, with_grad=True):
+            mix_logits = ops.linear_skinny_grad(parts, self.mix.weight, self.mix.bias)
+        elif ops.linear_skinny_supported(parts, self.mix.weight):  # the 1 + nmem mixing logits straight from the three inputs: no concatenation, no N = 3 GEMM tile
             mix_logits = ops.linear_skinny(parts, self.mix.weight, self.mix.bias)
         else:
             mix_logits = ops.linear(torch.cat(parts, dim=-1), self.mix.weight, self.mix.bias, out_dtype=torch.float32)
@@ -736,8 +745,8 @@ class TransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0, decode_rules=None, segments=None):
+                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
         if isinstance(source_maps, (list, tuple)):
             source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
         return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)

@@ -1146,6 +1146,7 @@ struct ScoreArgs {
   const int64_t* targets;   // [R]
   float* prob;              // [R]
   float* ptr;               // [R] or null: the pointer part of prob
+  float* stats;             // [R, 2] or null: the row's final (max, sum) of the online softmax (case_pointer_head_score_stats)
   int64_t V, S, rows_per_source, pad;
   int nmem;
 };
@@ -1177,6 +1178,7 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const Sc
     if (tid == 0) {
       a.prob[r] = is_pad ? 1.f : 0.f;
       if (a.ptr) a.ptr[r] = 0.f;
+      if (a.stats) a.stats[2 * r] = a.stats[2 * r + 1] = 0.f;
     }
     return;
   }
@@ -1259,7 +1261,143 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const Sc
   if (lane == 0) {
     a.prob[r] = pm[0] * gen_y + acc;
     if (a.ptr) a.ptr[r] = acc;
+    if (a.stats) {
+      a.stats[2 * r] = m;
+      a.stats[2 * r + 1] = s;
+    }
   }
+}
+
+// ---- K41: the backward of K29 ---------------------------------------------------------------------------------------------------------------
+// d prob[r] / d (logits, mix_logits, copy_k) times g[r], from the forward's saved (max, sum) and prob.  One workgroup of 256 threads per
+// row.  A short pass over the S source positions reads the item's UNSORTED ids: position s of memory k holds y or it does not, so
+// d_copy_k[r, s] is one compare (no search, no read-after-write on the row) and c_k, the copy mass of y in memory k, is a per-thread sum
+// that meets in the fixed xor tree per wave and in wave order across the four waves.  Then one pass over V: gen_v = exp(l_v - m) / s is
+// K29's own expression for gen_y, read with K29's head / body / tail peel (non-temporal: the logits are used once here too) and stored
+// 16 bytes wide with the DEFAULT policy -- the two vocabulary GEMMs of the Linear backward read d_logits next.  Where the gradient row
+// does not share the logits row's 16-byte phase (a caller's offset view) the pass falls back to 4-byte accesses.  Every output element
+// is written, a row that is not scored writes zeros; no atomics: two launches give the same bits.
+struct ScoreBwdArgs {
+  const float* logits;      // [R, V]
+  const float* mix_logits;  // [R, 1 + nmem]
+  const int64_t* ids;       // [R / rows_per_source, S] the unsorted source ids
+  const float* copy[PH_MAX_MEM];  // copy_k [R, len_k]
+  int64_t len[PH_MAX_MEM];
+  const int64_t* targets;   // [R]
+  const float* stats;       // [R, 2] the forward's (max, sum)
+  const float* prob;        // [R] the forward's output
+  const float* g;           // [R] dL / dprob
+  float* d_logits;          // [R, V]
+  float* d_mix;             // [R, 1 + nmem]
+  float* d_copy[PH_MAX_MEM];  // [R, len_k]
+  int64_t V, S, rows_per_source, pad;
+  int nmem;
+};
+
+// the memory that holds source position s and the position inside it
+__device__ __forceinline__ int ps_locate(const ScoreBwdArgs& a, int64_t& pos) {
+  int k = 0;
+#pragma unroll
+  for (int j = 0; j < PH_MAX_MEM - 1; ++j) {
+    if (k == j && j + 1 < a.nmem && pos >= a.len[j]) {
+      pos -= a.len[j];
+      k = j + 1;
+    }
+  }
+  return k;
+}
+
+__global__ __launch_bounds__(PS_THREADS) void pointer_head_score_bwd_kernel(const ScoreBwdArgs a) {
+  __shared__ float red_c[PS_THREADS / 64][PH_MAX_MEM];
+  const int64_t r = blockIdx.x, V = a.V, S = a.S;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int64_t y = a.targets[r];
+  const bool is_pad = a.pad >= 0 && y == a.pad;
+  const bool scored = !(is_pad || y < 0 || y >= V);  // (uniform over the workgroup)
+  const float* lg = a.logits + r * V;
+  float* dl = a.d_logits + r * V;
+  const float gr = scored ? a.g[r] : 0.f;
+  // the mixing probabilities, as in K29
+  float pm[1 + PH_MAX_MEM];
+  {
+    float mm = -INFINITY, ss = 0.f;
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) pm[k] = k <= a.nmem ? a.mix_logits[r * (a.nmem + 1) + k] : -INFINITY;
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) mm = fmaxf(mm, pm[k]);
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) {
+      pm[k] = __expf(pm[k] - mm);
+      ss += pm[k];
+    }
+#pragma unroll
+    for (int k = 0; k <= PH_MAX_MEM; ++k) pm[k] /= ss;
+  }
+  // the pass over S: d_copy_k and the per-memory copy mass of y
+  float c[PH_MAX_MEM];
+#pragma unroll
+  for (int k = 0; k < PH_MAX_MEM; ++k) c[k] = 0.f;
+  const int64_t* ids = a.ids + (r / a.rows_per_source) * S;
+  for (int64_t s0 = tid; s0 < S; s0 += PS_THREADS) {
+    int64_t pos = s0;
+    const int k = ps_locate(a, pos);
+    const bool hit = scored && ids[s0] == y;
+#pragma unroll
+    for (int j = 0; j < PH_MAX_MEM; ++j) {
+      if (j == k) {
+        const int64_t at = r * a.len[j] + pos;
+        a.d_copy[j][at] = hit ? gr * pm[j + 1] : 0.f;
+        if (hit) c[j] += a.copy[j][at];
+      }
+    }
+  }
+  if (!scored) {  // zeros everywhere (d_copy is done)
+    if (tid <= a.nmem) a.d_mix[r * (a.nmem + 1) + tid] = 0.f;
+    for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = 0.f;
+    return;
+  }
+#pragma unroll
+  for (int k = 0; k < PH_MAX_MEM; ++k) {
+    c[k] = wave_sum(c[k]);
+    if (lane == 0) red_c[tid >> 6][k] = c[k];
+  }
+  __syncthreads();
+  const float m = a.stats[2 * r], s = a.stats[2 * r + 1];
+  const float gen_y = __expf(lg[y] - m) / s;
+  if (tid == 0) {
+    const float p = a.prob[r];
+    a.d_mix[r * (a.nmem + 1)] = (gr * pm[0]) * (gen_y - p);
+#pragma unroll
+    for (int k = 0; k < PH_MAX_MEM; ++k) {
+      if (k < a.nmem) {
+        float ck = red_c[0][k];
+#pragma unroll
+        for (int w = 1; w < PS_THREADS / 64; ++w) ck += red_c[w][k];
+        a.d_mix[r * (a.nmem + 1) + 1 + k] = (gr * pm[1 + k]) * (ck - p);
+      }
+    }
+  }
+  // the pass over V
+  const float coef = gr * pm[0] * gen_y;
+  if (((reinterpret_cast<uintptr_t>(lg) ^ reinterpret_cast<uintptr_t>(dl)) & 15u) != 0) {  // rows out of phase: 4-byte accesses
+    for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = coef * ((v == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + v) - m) / s);
+    return;
+  }
+  int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
+  if (head > V) head = V;
+  const int64_t n4 = (V - head) >> 2, tail = head + 4 * n4;
+  if (tid < head) dl[tid] = coef * ((tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tid) - m) / s);
+  const float* body = lg + head;
+#pragma unroll 2
+  for (int64_t i = tid; i < n4; i += PS_THREADS) {
+    const ps_f32x4 x = PS_LOAD4(body + 4 * i);
+    const int64_t v0 = head + 4 * i;
+    ps_f32x4 d;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) d[e] = coef * ((v0 + e == y ? 1.f : 0.f) - __expf(x[e] - m) / s);
+    *reinterpret_cast<ps_f32x4*>(dl + v0) = d;
+  }
+  if (tail + tid < V) dl[tail + tid] = coef * ((tail + tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tail + tid) - m) / s);
 }
 
 // ---- K11 ---------------------------------------------------------------------------------------
@@ -1951,22 +2089,77 @@ extern "C" int case_row_rules(float* dist, const uint8_t* ended, int64_t R, int6
   return case_check_launch("case_row_rules");
 }
 
-extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
-                                       const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
-                                       float* prob, float* copy, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
-  CASE_REQUIRE(targets && prob, "case_pointer_head_score: bad argument");
-  CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "case_pointer_head_score: %lld rows are no multiple of rows_per_source %lld",
-               (long long)R, (long long)rows_per_source);
+static int pointer_head_score_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                     const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                     float* prob, float* copy, float* stats, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  CASE_REQUIRE(targets && prob, "%s: bad argument", who);
+  CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "%s: %lld rows are no multiple of rows_per_source %lld", who, (long long)R,
+               (long long)rows_per_source);
   ScoreArgs a;
-  const int rc = pointer_head_fill(a, "case_pointer_head_score", logits, mix_logits, keys, copies, lens, nmem, R, V, S, PS_MAX_V, "");
+  const int rc = pointer_head_fill(a, who, logits, mix_logits, keys, copies, lens, nmem, R, V, S, PS_MAX_V, "");
   if (rc != CASE_OK) return rc;
   a.targets = targets;
   a.prob = prob;
   a.ptr = copy;
+  a.stats = stats;
   a.rows_per_source = rows_per_source;
   a.pad = pad;
   hipLaunchKernelGGL(pointer_head_score_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
-  return case_check_launch("case_pointer_head_score");
+  return case_check_launch(who);
+}
+
+extern "C" int case_pointer_head_score(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                       const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                       float* prob, float* copy, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  return pointer_head_score_launch("case_pointer_head_score", logits, mix_logits, keys, rows_per_source, copies, lens, nmem, targets, pad, prob, copy,
+                                   nullptr, R, V, S, stream);
+}
+
+extern "C" int case_pointer_head_score_stats(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                             const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                             float* prob, float* copy, float* stats, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  return pointer_head_score_launch("case_pointer_head_score_stats", logits, mix_logits, keys, rows_per_source, copies, lens, nmem, targets, pad, prob,
+                                   copy, stats, R, V, S, stream);
+}
+
+extern "C" int case_pointer_head_score_bwd(const float* logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                                           const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                           const float* stats, const float* prob, const float* g, float* d_logits, float* d_mix,
+                                           float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  const char* who = "case_pointer_head_score_bwd";
+  CASE_REQUIRE(logits && mix_logits && ids && copies && lens && targets && stats && prob && g && d_logits && d_mix && d_copies && R > 0 && V > 0 &&
+                   S > 0 && nmem >= 1 && R < (1ll << 31),
+               "%s: bad argument", who);
+  CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "%s: %lld rows are no multiple of rows_per_source %lld", who, (long long)R,
+               (long long)rows_per_source);
+  if (nmem > PH_MAX_MEM || V > PS_MAX_V || S > 32768)
+    return case_set_error(CASE_E_UNSUPPORTED, "%s: built for <= %d memories, V <= %lld, S <= 32768", who, PH_MAX_MEM, (long long)PS_MAX_V);
+  ScoreBwdArgs a;
+  int64_t total = 0;
+  for (int m = 0; m < PH_MAX_MEM; ++m) {
+    CASE_REQUIRE(m >= nmem || (copies[m] && d_copies[m] && lens[m] > 0), "%s: null copy weights", who);
+    a.copy[m] = m < nmem ? copies[m] : nullptr;
+    a.d_copy[m] = m < nmem ? d_copies[m] : nullptr;
+    a.len[m] = m < nmem ? lens[m] : 0;
+    total += a.len[m];
+  }
+  CASE_REQUIRE(total == S, "%s: the memories hold %lld positions, the source map %lld", who, (long long)total, (long long)S);
+  a.logits = logits;
+  a.mix_logits = mix_logits;
+  a.ids = ids;
+  a.targets = targets;
+  a.stats = stats;
+  a.prob = prob;
+  a.g = g;
+  a.d_logits = d_logits;
+  a.d_mix = d_mix;
+  a.V = V;
+  a.S = S;
+  a.rows_per_source = rows_per_source;
+  a.pad = pad;
+  a.nmem = nmem;
+  hipLaunchKernelGGL(pointer_head_score_bwd_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
+  return case_check_launch(who);
 }
 
 extern "C" int case_copy_scatter_fwd(const int64_t* src, const float* w, float* dist, int64_t B, int64_t T, int64_t S,

@@ -3,7 +3,8 @@
 n-gram overlap of an answer with its passages, on the host (``bleu``) and on the device (``ngram_ids``); METEOR with its exact stage on
 ids and one caller-provided class table, on the host (``meteor``) and on the device (``meteor_ids``); the TREC ranking metrics of the
 passage scores, on the host (``trec``) and on the device (``rank_ids``); the token-level counts of the supporting-token stage on the device
-(``token_ids``); answer attribution -- which passage each answer token was copied from -- on the device (``attribution``)."""
+(``token_ids``); answer attribution -- which passage each answer token was copied from -- on the device (``attribution``); the expected
+cost of a pool of candidates under the model's posterior and the minimum-risk training step built on it (``risk``)."""
 from .rouge import eval_rouge_l, lcs_length, rouge_l  # noqa: F401
 from .rouge_ids import consensus, eval_rouge_l_ids, rouge_l_ids  # noqa: F401
 from .bleu import eval_bleu, modified_precision, ngram_overlap, sentence_bleu  # noqa: F401
@@ -15,3 +16,4 @@ from .rank_ids import eval_rank_ids, rank_metrics_ids  # noqa: F401
 from .token_ids import eval_token_ids, token_metrics_ids  # noqa: F401
 from .attribution import (attribution_ids, copy_attribution_host, eval_attribution_ids, source_segments,  # noqa: F401
                           summarize as summarize_attribution)
+from .risk import assemble_pool, dedup_valid, minimum_risk_step, pool_cost, sequence_risk_host  # noqa: F401

@@ -1949,8 +1949,9 @@ def _ban_operands_wide(ban, rows, who):
 LINEAR_SKINNY = os.environ.get("CASE_LINEAR_SKINNY", "auto")  # "off": torch.cat + the GEMM path (A/B)
 
 
-def linear_skinny_supported(xs, w):
-    return (LINEAR_SKINNY != "off" and 1 <= len(xs) <= 4 and 1 <= w.shape[0] <= 8 and not torch.is_grad_enabled()
+def linear_skinny_supported(xs, w, with_grad=False):
+    """``with_grad``: for ``linear_skinny_grad`` (the same forward with autograd behind it); otherwise inference under no_grad only."""
+    return (LINEAR_SKINNY != "off" and 1 <= len(xs) <= 4 and 1 <= w.shape[0] <= 8 and (with_grad or not torch.is_grad_enabled())
             and all(x.is_cuda and x.dtype == xs[0].dtype and x.shape[:-1] == xs[0].shape[:-1] for x in xs)
             and xs[0].dtype in (torch.float32, torch.bfloat16) and sum(x.shape[-1] for x in xs) == w.shape[1]
             and bool(A.lib.case_abi_features() & A.FEAT_LINEAR_SKINNY))
@@ -1970,6 +1971,45 @@ def linear_skinny(xs, w, b=None):
     A.call("case_linear_skinny", C.cast(ptrs, C.c_void_p), C.cast(widths, C.c_void_p), n, _ptr(w32), _ptr(b32), _ptr(y), rows, w.shape[0], _code(xs[0]),
            _stream())
     return y
+
+
+class LinearSkinnyFn(Function):
+    """``linear_skinny`` with autograd: the forward is the same launch (the same bits as the no_grad pass), the backward the two GEMMs of
+    ``LinearFn`` on the concatenated inputs -- dX = g W split by the inputs' widths, dW = g^T cat(xs) with the bias gradient beside it."""
+
+    @staticmethod
+    def forward(ctx, w, b, *xs):
+        xs = [x if x.is_contiguous() else x.contiguous() for x in xs]
+        ctx.save_for_backward(w, *xs)
+        ctx.has_b = b is not None
+        return linear_skinny(xs, w, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        w, xs = ctx.saved_tensors[0], ctx.saved_tensors[1:]
+        N, K = w.shape
+        x2 = torch.cat([x.reshape(-1, x.shape[-1]) for x in xs], dim=-1)
+        M = x2.shape[0]
+        g2 = cast(g.reshape(M, N).contiguous(), x2.dtype)
+        dxs = [None] * len(xs)
+        if any(ctx.needs_input_grad[2:]):
+            dx = _input_grad(g2, cast_param(w, x2.dtype), M, K, N)
+            dxs = [d.reshape(x.shape) for d, x in zip(dx.split([x.shape[-1] for x in xs], dim=-1), xs)]
+        dw = db = None
+        want_w, want_b = ctx.needs_input_grad[0], ctx.has_b and ctx.needs_input_grad[1]
+        if want_w and want_b:
+            dw, db = _zeros_like_shapes(g2.device, (N, K), (N,))
+            _weight_grad(g2, x2, N, K, out=dw, bias_out=db)
+        elif want_w:
+            dw = _weight_grad(g2, x2, N, K)
+        elif want_b:
+            db = _colsum(g2)
+        return (dw, db) + tuple(dxs)
+
+
+def linear_skinny_grad(xs, w, b=None):
+    """``linear_skinny`` (same kernel, same bits) as a differentiable op, for a scoring pass that is differentiated."""
+    return LinearSkinnyFn.apply(w, b, *xs)
 
 
 def _head_operands(logits, mix_logits, source_map, copies):
@@ -2229,6 +2269,151 @@ def pointer_head_score(logits, mix_logits, source_map, rows_per_source, copies, 
     A.call("case_pointer_head_score", _ptr(logits), _ptr(mix_logits), _ptr(keys), rows_per_source, ptrs, lens, n, _ptr(targets), int(pad), _ptr(prob),
            _ptr(copy), R, V, S, _stream())
     return prob, copy
+
+
+# K41: K29 with autograd behind it, for a scoring pass that is differentiated (minimum-risk training).  The forward is K29's kernel with the
+# row's (max, sum) kept; the backward is one launch that writes the gradient of the logits, of the mixing logits and of every memory's copy
+# weights.  ``pointer_score_supported`` / ``pointer_head_score`` stay the no-grad pair: only a caller that asks for this head gets it.
+def pointer_score_grad_supported(source_map, nmem):
+    return (POINTER_SCORE != "off" and isinstance(source_map, SortedSource) and 1 <= nmem <= 4
+            and bool(A.lib.case_abi_features() & A.FEAT_RISK_TRAIN))
+
+
+def _copy_pointers(tensors):
+    return C.cast((C.c_void_p * len(tensors))(*[t.data_ptr() for t in tensors]), C.c_void_p)
+
+
+def pointer_head_score_bwd(logits, mix_logits, ids, rows_per_source, copies, targets, pad, stats, prob, g, out=None):
+    """K41 as a plain launch: contiguous f32 logits [R, V], mix_logits [R, 1 + nmem], copies [R, len_k], stats [R, 2], prob [R] and g [R];
+    ids int64 [R / rows_per_source, S] (``SortedSource.ids``); targets int64 [R] -> (d_logits [R, V], d_mix [R, 1 + nmem], [d_copy_k
+    [R, len_k]]), every element written.  ``out``: that triple as buffers to write into."""
+    R, V = logits.shape
+    d_logits, d_mix, d_cs = out if out is not None else (torch.empty_like(logits), torch.empty_like(mix_logits), [torch.empty_like(c) for c in copies])
+    for t in [logits, mix_logits, stats, prob, g, d_logits, d_mix] + list(copies) + list(d_cs):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("pointer_head_score_bwd: contiguous f32 tensors")
+    if (ids.dtype != torch.int64 or not ids.is_contiguous() or ids.shape[0] * rows_per_source != R or targets.dtype != torch.int64 or targets.numel() != R
+            or tuple(mix_logits.shape) != (R, len(copies) + 1) or tuple(stats.shape) != (R, 2) or prob.numel() != R or g.numel() != R
+            or d_logits.shape != logits.shape or d_mix.shape != mix_logits.shape or len(d_cs) != len(copies)
+            or any(c.shape != d.shape or c.dim() != 2 or c.shape[0] != R for c, d in zip(copies, d_cs))):
+        raise ValueError("pointer_head_score_bwd: shapes do not fit R = %d rows of V = %d" % (R, V))
+    lens = C.cast((C.c_int64 * len(copies))(*[c.shape[1] for c in copies]), C.c_void_p)
+    A.call("case_pointer_head_score_bwd", _ptr(logits), _ptr(mix_logits), _ptr(ids), int(rows_per_source), _copy_pointers(copies), lens, len(copies),
+           _ptr(targets), int(pad), _ptr(stats), _ptr(prob), _ptr(g), _ptr(d_logits), _ptr(d_mix), _copy_pointers(d_cs), R, V, ids.shape[1], _stream())
+    return d_logits, d_mix, d_cs
+
+
+class PointerScoreFn(Function):
+    @staticmethod
+    def forward(ctx, logits, mix_logits, source_map, rows_per_source, targets, pad, *copies):
+        R, V = logits.shape
+        mix_dtype = mix_logits.dtype
+        logits, mix_logits, cs, ptrs, lens, n, S = _head_operands(logits, mix_logits, source_map, copies)
+        prob = torch.empty(R, dtype=torch.float32, device=logits.device)
+        copy = torch.empty(R, dtype=torch.float32, device=logits.device)
+        stats = torch.empty(R, 2, dtype=torch.float32, device=logits.device)
+        A.call("case_pointer_head_score_stats", _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), rows_per_source, ptrs, lens, n, _ptr(targets),
+               pad, _ptr(prob), _ptr(copy), _ptr(stats), R, V, S, _stream())
+        ctx.save_for_backward(logits, mix_logits, targets, stats, prob, source_map.ids, *cs)
+        ctx.meta = (rows_per_source, pad, [c.dtype for c in copies], mix_dtype)
+        ctx.mark_non_differentiable(copy, stats)
+        return prob, copy, stats
+
+    @staticmethod
+    def backward(ctx, g, _g_copy, _g_stats):
+        logits, mix_logits, targets, stats, prob, ids = ctx.saved_tensors[:6]
+        cs = list(ctx.saved_tensors[6:])
+        rows_per_source, pad, copy_dtypes, mix_dtype = ctx.meta
+        R, V = logits.shape
+        d_logits, d_mix, d_cs = pointer_head_score_bwd(logits, mix_logits, ids, rows_per_source, cs, targets, pad, stats, prob, g.float().contiguous())
+        return (d_logits, d_mix.to(mix_dtype), None, None, None, None) + tuple(d.to(dt) for d, dt in zip(d_cs, copy_dtypes))
+
+
+def pointer_head_score_grad(logits, mix_logits, source_map, rows_per_source, copies, targets, pad=0):
+    """``pointer_head_score`` with autograd (K29 with row statistics forward, K41 backward): the same arguments -> (prob f32 [R], copy f32
+    [R]) with K29's bits.  ``prob`` is differentiable in ``logits``, ``mix_logits`` and every ``copies[k]``; ``copy`` is not.  The forward
+    keeps the logits, the mixing logits, the copy weights, the targets, the row statistics [R, 2] and prob for the backward pass
+    (``PointerScoreFn`` itself also returns the statistics: the row's (max, sum exp(logit - max)), (0, 0) for a row that is not scored)."""
+    if logits.dtype != torch.float32 or logits.dim() != 2:
+        raise TypeError("pointer_head_score_grad: logits must be f32 [R, V]")
+    if not isinstance(source_map, SortedSource):
+        raise TypeError("pointer_head_score_grad: source_map must be a SortedSource")
+    if not bool(A.lib.case_abi_features() & A.FEAT_RISK_TRAIN):
+        raise RuntimeError("pointer_head_score_grad: this build of the library lacks K41 (CASE_FEAT_RISK_TRAIN)")
+    R, V = logits.shape
+    rows_per_source = int(rows_per_source)
+    keys = source_map.keys
+    if rows_per_source < 1 or R % rows_per_source or keys.shape[0] * rows_per_source != R:
+        raise ValueError("pointer_head_score_grad: %d rows, %d key rows, rows_per_source %d" % (R, keys.shape[0], rows_per_source))
+    if targets.dtype != torch.int64 or targets.numel() != R:
+        raise TypeError("pointer_head_score_grad: targets must be int64 [R]")
+    if not 1 <= len(copies) <= 4:
+        raise ValueError("pointer_head_score_grad: 1 .. 4 memories (got %d)" % len(copies))
+    if tuple(mix_logits.shape) != (R, len(copies) + 1):
+        raise ValueError("pointer_head_score_grad: mix_logits must be [R, 1 + nmem]")
+    if any(c.dim() != 2 or c.shape[0] != R for c in copies):
+        raise ValueError("pointer_head_score_grad: every copies[k] must be [R, len_k]")
+    if sum(c.shape[1] for c in copies) != keys.shape[1]:
+        raise ValueError("pointer_head_score_grad: the memories hold %d positions, the source map %d" % (sum(c.shape[1] for c in copies), keys.shape[1]))
+    prob, copy, _ = PointerScoreFn.apply(logits, mix_logits, source_map, rows_per_source, targets.reshape(R).contiguous(), int(pad), *copies)
+    return prob, copy
+
+
+# K42: the expected cost of a pool of candidates under the renormalised model posterior (evaluation/risk.py states the rule).
+RISK_MAX_N, RISK_MAX_T = 64, 1024
+
+
+def check_risk_alpha(alpha, who="sequence_risk"):
+    alpha = float(alpha)
+    if not (alpha >= 0.0 and math.isfinite(alpha)):
+        raise ValueError("%s: alpha must be >= 0 and finite (got %r)" % (who, alpha))
+    return alpha
+
+
+class SequenceRiskFn(Function):
+    @staticmethod
+    def forward(ctx, token_probs, scored, cost, valid, alpha):
+        B, N, T = token_probs.shape
+        p = token_probs.float().contiguous()
+        dev = p.device
+        risk = torch.empty(B, dtype=torch.float32, device=dev)
+        q = torch.empty(B, N, dtype=torch.float32, device=dev)
+        grad_p = torch.empty(B, N, T, dtype=torch.float32, device=dev)
+        A.call("case_sequence_risk", _ptr(p), _ptr(_u8(scored)), _ptr(cost), _ptr(_u8(valid)), alpha, _ptr(risk), _ptr(q), _ptr(grad_p), B, N, T,
+               _stream())
+        ctx.save_for_backward(grad_p)
+        ctx.in_dtype = token_probs.dtype
+        ctx.mark_non_differentiable(q)
+        return risk, q
+
+    @staticmethod
+    def backward(ctx, g, _g_q):
+        (grad_p,) = ctx.saved_tensors
+        return (grad_p * g.float().reshape(-1, 1, 1)).to(ctx.in_dtype), None, None, None, None
+
+
+def sequence_risk(token_probs, scored, cost, valid=None, alpha=5e-3, want_q=False):
+    """K42: token_probs f32 [B, N, T] (the model's probability of every token of N candidates per item), scored bool [B, N, T] (the
+    positions that count), cost f32 [B, N], valid bool [B, N] or None (all) -> risk f32 [B] = sum_n Q_n cost_n with Q = softmax over the
+    valid n of alpha sum_t ln max(p, 1e-30) (``evaluation.risk``; f64 inside, rounded once).  ``risk`` is differentiable in ``token_probs``:
+    the forward keeps grad_p [B, N, T], the backward scales it by the upstream [B] gradient.  ``want_q``: (risk, q f32 [B, N]).  N <= 64,
+    T <= 1024; an item without a valid candidate has risk 0 and no gradient."""
+    if token_probs.dim() != 3 or not token_probs.is_floating_point():
+        raise TypeError("sequence_risk: token_probs must be a float tensor [B, N, T]")
+    B, N, T = token_probs.shape
+    if scored.dtype not in (torch.bool, torch.uint8) or tuple(scored.shape) != (B, N, T):
+        raise TypeError("sequence_risk: scored must be bool [B, N, T]")
+    if cost.dim() != 2 or tuple(cost.shape) != (B, N) or not cost.is_floating_point():
+        raise TypeError("sequence_risk: cost must be a float tensor [B, N]")
+    if valid is not None and (valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, N)):
+        raise TypeError("sequence_risk: valid must be bool [B, N]")
+    alpha = check_risk_alpha(alpha)
+    if N > RISK_MAX_N or T > RISK_MAX_T:
+        raise ValueError("sequence_risk: pools of up to %d candidates of up to %d positions (got %d x %d)" % (RISK_MAX_N, RISK_MAX_T, N, T))
+    if not bool(A.lib.case_abi_features() & A.FEAT_RISK_TRAIN):
+        raise RuntimeError("sequence_risk: this build of the library lacks K42 (CASE_FEAT_RISK_TRAIN)")
+    risk, q = SequenceRiskFn.apply(token_probs, scored.contiguous(), cost.detach().float().contiguous(), valid, alpha)
+    return (risk, q) if want_q else risk
 
 
 # K32: the n-gram ban.  The fused heads apply it behind their row build (``ban=`` above); ``ngram_ban_`` is the same rule as a launch of its own.

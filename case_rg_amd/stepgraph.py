@@ -79,6 +79,8 @@ class StepGraphs(object):
         tr = self.trainer
         if not isinstance(optimizer, FusedAdam) or tr.accumulation_steps != 1 or tr.step_state is None:
             return None
+        if method == "mrt_train":
+            return None  # (a minimum-risk step draws its pool inside the step: it runs eagerly, capture is out of scope)
         if any(torch.is_tensor(v) and not v.is_cuda for v in data.values()):
             return None  # (a host tensor would be uploaded inside the step: not capturable)
         r = data.get("response")

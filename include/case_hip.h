@@ -82,7 +82,8 @@ enum {
   CASE_FEAT_DECODE_RULES = 1u << 26,      /* min_length / banned ids / beam length penalty: the `_rules` forms of K23 / K24 / K25 / K28, case_row_rules */
   CASE_FEAT_TOKEN_LABELS = 1u << 27,      /* K37 / K38 case_token_labels / case_token_select */
   CASE_FEAT_COPY_ATTRIBUTION = 1u << 28,  /* K39 case_copy_attribution */
-  CASE_FEAT_METEOR = 1u << 29             /* K40 case_meteor */
+  CASE_FEAT_METEOR = 1u << 29,            /* K40 case_meteor */
+  CASE_FEAT_RISK_TRAIN = 1u << 30         /* K41 / K42 case_pointer_head_score_stats / _bwd, case_sequence_risk */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -926,6 +927,39 @@ int case_copy_attribution(const float* mix_logits, const uint32_t* keys, int64_t
 int case_meteor(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, const int32_t* classes, int64_t V, double alpha,
                 double beta, double gamma, int32_t* counts, float* meteor_pair, double* meteor, int32_t* best_ref, int32_t* align, int64_t B,
                 int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Minimum-risk training (CASE_FEAT_RISK_TRAIN; purely additive, generation 600 unchanged): the differentiable score head and the
+ * expected cost of a pool of candidates under the renormalised model posterior (evaluation/risk.py states the rule).
+ * case_pointer_head_score_stats: K29 (case_pointer_head_score: same operands, same kernel, same prob / copy bits) with one more nullable
+ *   output, stats f32 [R, 2] = the row's final (max, sum exp(logit - max)) of the online softmax; (0, 0) for a row that is not scored
+ *   (target == pad or outside [0, V)).
+ * K41 case_pointer_head_score_bwd: the gradient of prob.  K29's operands; ids int64 [R / rows_per_source, S] = the UNSORTED source ids the
+ *   keys were sorted from; stats and prob as the forward wrote them; g f32 [R] = dL/dprob.  For row r with y = targets[r] scored, pm and
+ *   gen_v = exp(logits[r, v] - stats[r, 0]) / stats[r, 1] as in K29, c_k = sum of copies[k][r, s] over the positions s of memory k with id y:
+ *     d_logits[r, v] = g pm[0] gen_y ((v == y) - gen_v)                          f32 [R, V]
+ *     d_mix[r, j]    = g pm[j] (a_j - prob[r]),  a_0 = gen_y, a_{1+k} = c_k      f32 [R, 1 + nmem]
+ *     d_copies[k][r, s] = g pm[1 + k] where the id at that position is y, else 0 f32 [R, len_k]
+ *   A row that is not scored writes zeros everywhere: every output element is written.  One workgroup per row, the logits read once,
+ *   no atomics, reductions in a fixed order: two launches give the same bits.  Limits as K29 (nmem <= 4, S <= 32768, V <= 131071;
+ *   CASE_E_UNSUPPORTED otherwise).
+ * K42 case_sequence_risk: token_probs f32 [B, N, T], scored uint8 [B, N, T], cost f32 [B, N], valid uint8 [B, N] (NULL: all).  Per item,
+ *   over the valid candidates n:  l_n = sum_{scored t} ln max(p[n, t], 1e-30);  Q_n = softmax_n(alpha l_n) (0 where invalid);
+ *   risk = sum_n Q_n cost_n;  grad_p[n, t] = alpha Q_n (cost_n - risk) / p[n, t] on scored positions with p > 1e-30, else 0.  f64
+ *   throughout, every output rounded to f32 once: risk [B], q [B, N], grad_p [B, N, T].  An item without a valid candidate: all zeros.
+ *   alpha >= 0 and finite (CASE_E_ARG otherwise); N <= 64, T <= 1024 (CASE_E_UNSUPPORTED otherwise).  One wave per item, no atomics:
+ *   two launches give the same bits.
+ * All three are asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+int case_pointer_head_score_stats(const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                  const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                  float* prob, float* copy, float* stats, int64_t R, int64_t V, int64_t S, case_stream_t stream);
+int case_pointer_head_score_bwd(const float* logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                                const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                const float* stats, const float* prob, const float* g, float* d_logits, float* d_mix, float* const* d_copies,
+                                int64_t R, int64_t V, int64_t S, case_stream_t stream);
+int case_sequence_risk(const float* token_probs, const uint8_t* scored, const float* cost, const uint8_t* valid, double alpha, float* risk,
+                       float* q, float* grad_p, int64_t B, int64_t N, int64_t T, case_stream_t stream);
 
 #ifdef __cplusplus
 }
