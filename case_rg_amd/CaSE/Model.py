@@ -180,7 +180,7 @@ class CaSE(nn.Module):
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
-        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30) or "bleu" (K34 + K35, BLEU-4 with add-one smoothing)
+        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30), "bleu" (K34 + K35, BLEU-4 with add-one smoothing), "rouge_1" / "rouge_2" (K34 + K44)
         # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
         # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
         self.no_repeat_ngram = 0
@@ -352,7 +352,7 @@ class CaSE(nn.Module):
         only the encode stages run for ``rank``.  ``valid`` bool [B, N] and ``weights`` f32 [B, N] (default uniform; e.g. the posterior
         exp(-length x ``sample_scores``)) as in ``evaluation.consensus``.  N <= 64, T <= 256, ids < 2^31; an empty candidate counts as [UNK].
         -> the pool's dict with ``answer`` [B, T] replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility`` [B, N] (-inf where
-        invalid) and ``pairwise_f`` [B, N, N].  ``metric`` ("rouge_l" or "bleu"; None: ``self.consensus_metric``) chooses the utility; under
+        invalid) and ``pairwise_f`` [B, N, N].  ``metric`` ("rouge_l", "bleu", "rouge_1" or "rouge_2"; None: ``self.consensus_metric``) chooses the utility; under
         "bleu" (sentence BLEU-4 with add-one smoothing) the matrix is returned as ``pairwise_bleu``.  Nothing is read back: with a sample pool
         at an integer ``seed`` the pass captures into one graph.  ``min_length`` / ``banned_ids`` (and ``length_penalty`` with ``pool="beam"``) go to
         the pool's decoder as ``no_repeat_ngram`` does (None: the model's attributes); explicit candidates take none of them."""

@@ -123,7 +123,7 @@ class Masque(nn.Module):
         self.beam_width = 4  # do_beam's default width
         self.sampling = dict(num_samples=1, temperature=1.0, top_k=0, top_p=1.0, seed=None)  # forward(data, method='sample') passes these to do_sample
         self.consensus_samples = 8  # do_consensus's default pool: this many samples per item
-        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30) or "bleu" (K34 + K35, BLEU-4 with add-one smoothing)
+        self.consensus_metric = "rouge_l"  # do_consensus's default utility: "rouge_l" (K30), "bleu" (K34 + K35, BLEU-4 with add-one smoothing), "rouge_1" / "rouge_2" (K34 + K44)
         # K32: greedy, beam and sampled decoding never emit an n-gram a hypothesis already holds (0 = off; the reference only truncates
         # afterwards, ``remove_duplicate``).  The ``no_repeat_ngram=`` keyword of do_test / do_beam / do_sample / do_consensus overrides it.
         self.no_repeat_ngram = 0
@@ -231,7 +231,7 @@ class Masque(nn.Module):
                      banned_ids=None, length_penalty=None, **sampling):
         """Consensus (minimum-Bayes-risk) selection under ROUGE-L over a sample pool, a beam pool or explicit ``candidates`` (eval mode only;
         see CaSE.do_consensus): the pool's dict with ``answer`` replaced by the pick, plus ``consensus_index`` [B], ``consensus_utility``
-        [B, N] and ``pairwise_f`` [B, N, N] (``metric="bleu"``: ``pairwise_bleu``; None: ``self.consensus_metric``).  ``min_length`` / ``banned_ids``
+        [B, N] and ``pairwise_f`` [B, N, N] (``metric="bleu"``: ``pairwise_bleu``, ``"rouge_1"`` / ``"rouge_2"``: ``pairwise_rouge_1`` / ``pairwise_rouge_2``; None: ``self.consensus_metric``).  ``min_length`` / ``banned_ids``
         (and ``length_penalty`` with ``pool="beam"``) go to the pool's decoder."""
         return consensus_answers(self, data, lambda d: self._encode_select(d)[2][0], pool, candidates, valid, weights,
                                  no_repeat_ngram=no_repeat_ngram, metric=metric, **self._pool_rules(pool, min_length, banned_ids, length_penalty), **sampling)

@@ -19,7 +19,7 @@ WS_ATTENTION_SPLITKV, WS_ATTENTION_BWD, WS_OPTIM_SUMSQ, WS_ENCODER_CHAIN_PACK, W
  FEAT_GEMM_DW_SLABS, FEAT_DECODER_CHAIN, FEAT_ATTN_DECODE_MQA, FEAT_POINTER_DECODE, FEAT_POINTER_HEAD, FEAT_GEMM_LN, FEAT_STEP_STATE,
  FEAT_INTERACTION, FEAT_ATTN_DECODE_APPEND, FEAT_LINEAR_SKINNY, FEAT_BEAM_DECODE, FEAT_SAMPLE_DECODE, FEAT_POINTER_SCORE, FEAT_CONSENSUS, FEAT_NGRAM_BAN,
  FEAT_NGRAM_COUNTS, FEAT_RANK_METRICS, FEAT_POINTER_HEAD_WIDE, FEAT_DECODE_RULES, FEAT_TOKEN_LABELS,
- FEAT_COPY_ATTRIBUTION, FEAT_METEOR, FEAT_RISK_TRAIN) = (1 << i for i in range(31))
+ FEAT_COPY_ATTRIBUTION, FEAT_METEOR, FEAT_RISK_TRAIN, FEAT_ROUGE_N) = (1 << i for i in range(32))  # (bit 31: the mask is full)
 EPI_BIAS_COL, EPI_BIAS_ROW, EPI_GELU, EPI_RELU = 1, 2, 4, 8
 EPI_RESIDUAL, EPI_MUL_DGELU, EPI_MUL_DRELU, EPI_ATOMIC, EPI_DROPOUT = 16, 32, 64, 128, 256
 
@@ -159,6 +159,8 @@ SIGNATURES = {
     "case_consensus_pick": [ptr] * 7 + [i64, i64, i64, ptr],
     "case_ngram_counts": [ptr] * 9 + [i64, i64, i64, i64, i64, i32, ptr],
     "case_bleu_scores": [ptr] * 7 + [i64, i64, i64, i32, i32, ptr],
+    "case_ngram_distinct": [ptr, ptr, ptr, i64, i64, i32, ptr],
+    "case_rouge_n_scores": [ptr] * 9 + [i64, i64, i64, i32, ptr],
     "case_rank_metrics": [ptr] * 8 + [i64, i64, i64, ptr],
     "case_token_labels": [ptr, ptr, ptr, i32, ptr, ptr, i64, i64, i64, i64, i64, i64, ptr],
     "case_token_select": [ptr] * 7 + [i64, i64, i32, ptr],

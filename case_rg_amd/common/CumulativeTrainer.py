@@ -270,14 +270,18 @@ class CumulativeTrainer(object):
         nll = float(total) / int(tokens)  # (the one read-back of the evaluation)
         return dict(nll=nll, perplexity=math.exp(nll), tokens=int(tokens))
 
-    def evaluate_rouge(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False):
+    def evaluate_rouge(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False, orders=()):
         """ROUGE-L of ``model(data, method)['answer']`` against ``data[references]`` (int64 [B, T'] or [B, M, T'], all-PAD rows = no ground truth
         there) without building a Python string: ``evaluation.eval_rouge_l_ids`` per batch, the sum kept on the device, one read-back at the
         end -> dict(rouge_l = the mean of the per-item best F x 100 rounded to 2 decimals -- ``evaluation.eval_rouge_l``'s number for
         ``predict`` + ``to_sentence`` --, items = the items counted).  ``remove_duplicates``: the answers go through the reference's
         ``remove_duplicate`` on the device first (K33): the number ``Run_Evaluation`` prints for ``save_result``'s answers.  One process, under no_grad in eval mode; the model's mode is restored
-        afterwards."""
+        afterwards.  ``orders``: ROUGE-N orders in 1..4 to report beside it from the same decoding pass, e.g. ``(1, 2)`` adds ``rouge_1`` and
+        ``rouge_2`` (``evaluation.eval_rouge_n_ids``: K34 + K43 + K44; ``evaluation.eval_rouge``'s ROUGE_1_F1 / ROUGE_2_F1), summed on the
+        device and rounded as ``rouge_l`` is; an order outside 1..4 is a ``ValueError`` before anything is decoded.  The default adds nothing."""
         from ..evaluation.rouge_ids import eval_rouge_l_ids, model_specials
+        from ..evaluation.rouge_n_ids import check_orders, eval_rouge_n_ids
+        orders = check_orders(orders, "evaluate_rouge")
         was_training = self.model.training
         self.model.eval()
         specials = model_specials(self.model.vocab2id)
@@ -289,13 +293,20 @@ class CumulativeTrainer(object):
                 for data in DevicePrefetcher(loader):
                     out = self.model(data, method=method)
                     part = eval_rouge_l_ids(out['answer'], data[references], specials, remove_duplicates).sum()
+                    if orders:
+                        by_order = eval_rouge_n_ids(out['answer'], data[references], specials, orders, remove_duplicates).sum(dim=0)
+                        part = torch.cat([part.view(1), by_order])
                     total = part if total is None else total + part
                     items += out['answer'].shape[0]
         finally:
             self.model.train(was_training)
+        names = tuple('rouge_%d' % k for k in orders)
         if items == 0:
-            return dict(rouge_l=float('nan'), items=0)
-        return dict(rouge_l=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
+            return dict({name: float('nan') for name in ('rouge_l',) + names}, items=0)
+        if not orders:
+            return dict(rouge_l=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
+        sums = total.tolist()  # (the one read-back of the evaluation)
+        return dict({name: round(s / items, 2) for name, s in zip(('rouge_l',) + names, sums)}, items=items)
 
     def evaluate_bleu(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False):
         """BLEU of ``model(data, method)['answer']`` against ``data[references]`` (as ``evaluate_rouge`` takes them), without building a Python
@@ -356,7 +367,8 @@ class CumulativeTrainer(object):
             return dict(meteor=float('nan'), items=0)
         return dict(meteor=round(float(total) / items, 2), items=items)  # (the one read-back of the evaluation)
 
-    GENERATION_METRICS = ('rouge_l', 'bleu', 'meteor')
+    GENERATION_METRICS = ('rouge_l', 'bleu', 'meteor')  # evaluate_generation's default
+    ROUGE_N_METRICS = {'rouge_1': 1, 'rouge_2': 2}      # further names it takes: the other two ROUGE figures of Run_Evaluation's line
 
     def evaluate_generation(self, dataset, collate_fn, batch_size, method='test', references='response', remove_duplicates=False,
                             metrics=GENERATION_METRICS, classes=None):
@@ -364,21 +376,25 @@ class CumulativeTrainer(object):
         named in ``metrics`` ('rouge_l', 'bleu', 'meteor') is computed from that pass's ``answer`` with the per-item function its
         single-metric method uses (``eval_rouge_l_ids``, ``eval_bleu_ids``, ``eval_meteor_ids``), the sums kept on the device, one read-back
         at the end -> dict(one entry per named metric, rounded exactly as ``evaluate_rouge`` / ``evaluate_bleu`` / ``evaluate_meteor`` round
-        it, items = the items counted).  An unknown metric name is a ``ValueError`` before anything is decoded.  ``remove_duplicates`` and
-        ``classes`` as in those methods.  One process, under no_grad in eval mode; the model's mode is restored afterwards."""
+        it, items = the items counted).  ``metrics`` may also name 'rouge_1' and 'rouge_2' (``eval_rouge_n_ids``, rounded as
+        ``evaluate_rouge(orders=...)`` rounds them): with 'rouge_l' the three ROUGE figures of the reference's ``eval_rouge``.  An unknown
+        metric name is a ``ValueError`` before anything is decoded.  ``remove_duplicates`` and ``classes`` as in those methods.  One process, under no_grad in eval mode; the model's mode is restored afterwards."""
         from ..evaluation.meteor_ids import eval_meteor_ids
         from ..evaluation.ngram_ids import eval_bleu_ids
         from ..evaluation.rouge_ids import eval_rouge_l_ids, model_specials
+        from ..evaluation.rouge_n_ids import eval_rouge_n_ids
         metrics = (metrics,) if isinstance(metrics, str) else tuple(metrics)
-        unknown = [name for name in metrics if name not in self.GENERATION_METRICS]
+        known = self.GENERATION_METRICS + tuple(self.ROUGE_N_METRICS)
+        unknown = [name for name in metrics if name not in known]
         if unknown or not metrics:
-            raise ValueError("evaluate_generation: metrics must name some of %s, not %r" % (self.GENERATION_METRICS, metrics))
+            raise ValueError("evaluate_generation: metrics must name some of %s, not %r" % (known, metrics))
         was_training = self.model.training
         self.model.eval()
         specials = model_specials(self.model.vocab2id)
         per_item = dict(rouge_l=lambda hyp, ref: eval_rouge_l_ids(hyp, ref, specials, remove_duplicates),
                         bleu=lambda hyp, ref: eval_bleu_ids(hyp, ref, specials, remove_duplicates=remove_duplicates),
                         meteor=lambda hyp, ref: eval_meteor_ids(hyp, ref, specials, classes, remove_duplicates=remove_duplicates))
+        orders = tuple(sorted({self.ROUGE_N_METRICS[name] for name in metrics if name in self.ROUGE_N_METRICS}))
         total, items = None, 0
         try:
             with torch.no_grad():
@@ -388,7 +404,10 @@ class CumulativeTrainer(object):
                     out = self.model(data, method=method)
                     if classes is not None and classes.device != out['answer'].device:
                         classes = classes.to(out['answer'].device)
-                    part = torch.stack([per_item[name](out['answer'], data[references]).sum() for name in metrics])
+                    if orders:  # (the named ROUGE-N orders share one K34 + K43 + K44 sequence)
+                        by_order = eval_rouge_n_ids(out['answer'], data[references], specials, orders, remove_duplicates).sum(dim=0)
+                    part = torch.stack([by_order[orders.index(self.ROUGE_N_METRICS[name])] if name in self.ROUGE_N_METRICS
+                                        else per_item[name](out['answer'], data[references]).sum() for name in metrics])
                     total = part if total is None else total + part
                     items += out['answer'].shape[0]
         finally:

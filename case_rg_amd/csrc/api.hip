@@ -29,7 +29,7 @@ extern "C" uint32_t case_abi_features(void) {
   return CASE_FEAT_GEMM_256 | CASE_FEAT_GEMM_SMALL | CASE_FEAT_ENCODER_CHAIN | CASE_FEAT_ATTN_SCORES | CASE_FEAT_ATTN_DECODE | CASE_FEAT_OPTIM |
          CASE_FEAT_ATTN_RESIDENT | CASE_FEAT_RESERVED_CUS | CASE_FEAT_GEMM_DW_SLABS | CASE_FEAT_ATTN_DECODE_MQA | CASE_FEAT_POINTER_DECODE | CASE_FEAT_POINTER_HEAD | CASE_FEAT_GEMM_LN | CASE_FEAT_STEP_STATE | CASE_FEAT_INTERACTION | CASE_FEAT_ATTN_DECODE_APPEND | CASE_FEAT_LINEAR_SKINNY |
          CASE_FEAT_BEAM_DECODE | CASE_FEAT_SAMPLE_DECODE | CASE_FEAT_POINTER_SCORE | CASE_FEAT_CONSENSUS | CASE_FEAT_NGRAM_BAN | CASE_FEAT_NGRAM_COUNTS | CASE_FEAT_RANK_METRICS | CASE_FEAT_POINTER_HEAD_WIDE |
-         CASE_FEAT_DECODE_RULES | CASE_FEAT_TOKEN_LABELS | CASE_FEAT_COPY_ATTRIBUTION | CASE_FEAT_METEOR | CASE_FEAT_RISK_TRAIN;
+         CASE_FEAT_DECODE_RULES | CASE_FEAT_TOKEN_LABELS | CASE_FEAT_COPY_ATTRIBUTION | CASE_FEAT_METEOR | CASE_FEAT_RISK_TRAIN | CASE_FEAT_ROUGE_N;
 }
 extern "C" const char* case_last_error(void) { return g_err; }
 

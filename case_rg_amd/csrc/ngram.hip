@@ -2,6 +2,9 @@
 //   K34 case_ngram_counts  per (hypothesis, reference) and per order k = 1..4: the clipped k-gram matches, the number of distinct hypothesis
 //                          k-grams that occur in the reference, and both against all present references at once; exact integers
 //   K35 case_bleu_scores   the counts -> sentence BLEU of every pair and against all present references (f64, fixed order)
+// and ROUGE-N, the set measure of the reference's Rouge.py rouge_n, from K34's hit / distinct and
+//   K43 case_ngram_distinct  the distinct k-grams of a row of any length (the reference side of ROUGE-N), k = 1..4; exact integers
+//   K44 case_rouge_n_scores  the counts -> F of every pair and F / P / R against the best present reference (f64, fixed order)
 // Nothing here waits for the host, and the library keeps no state.
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -235,7 +238,151 @@ __global__ __launch_bounds__(256) void bleu_scores_kernel(const int32_t* __restr
   if (bp) bp[h] = item_bp;
 }
 
+// ---- K43 -------------------------------------------------------------------------------------------------------------------------
+// The distinct k-grams of a row of any length (ROUGE-N's |R|): K34's self-pass over a row that does not fit 64 WORDS positions.  One wave per
+// row.  A WINDOW of 64 WORDS positions starting at s is held as K34 holds a hypothesis (lane l, word j: position s + l + 64 j, the sentinel -1
+// from the row's length on), and the row is streamed from position 0 to the window's end through ngram_step: a set bit of D_k(p) with
+// p below the bit's own position says "the k-gram that ends here ended at p already", and that position drops out (the masks are
+// wave-uniform, so D_k, the "behind p" masks and the dropped-out sets all live in scalar registers).  What is left is counted.
+// The seam: the D_k recurrence never sets a bit below k - 1 of a window, because that k-gram starts in the window before.  So consecutive
+// windows overlap by NGRAM_ORDERS - 1 = 3 positions (stride 64 WORDS - 3) and every window but the first counts its positions from 3 on: each
+// position of the row is counted in exactly one window, and there with its whole k-gram inside the window.  In the first window the
+// recurrence itself keeps order k from counting the positions below k - 1 of the row.
+// A row of L ids takes about L^2 / (2 (64 WORDS - 3)) token steps: quadratic, with the small constant of wave-wide mask arithmetic.
+constexpr int NGRAM_SEAM = NGRAM_ORDERS - 1;
+
+template <int WORDS>
+__global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_distinct_kernel(const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
+                                                                         int32_t* __restrict__ distinct, const int64_t rows, const int Tb,
+                                                                         const int max_n) {
+  constexpr int STRIDE = 64 * WORDS - NGRAM_SEAM;
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * NGRAM_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform, as in K34)
+  if (r >= rows) return;  // (whole waves: no barrier follows)
+  int len = b_len[r];
+  len = len < 0 ? 0 : len > Tb ? Tb : len;
+  const int64_t* __restrict__ row = b + r * Tb;
+  int total[NGRAM_ORDERS];
+#pragma unroll
+  for (int k = 0; k < NGRAM_ORDERS; ++k) total[k] = 0;
+  int s = 0;
+  do {
+    const int first = s > 0 ? NGRAM_SEAM : 0;                       // the window's first counted position
+    const int end = len - s < 64 * WORDS ? len : s + 64 * WORDS;  // one past the last position of the row that the window holds
+    int32_t tok[WORDS];
+    NgramMasks prev[WORDS];
+    unsigned long long earlier[NGRAM_ORDERS][WORDS];  // (wave-uniform like the D_k: the whole self-pass stays in scalar registers)
+#pragma unroll
+    for (int j = 0; j < WORDS; ++j) {
+      const int pos = s + lane + 64 * j;
+      tok[j] = pos < end ? (int32_t)row[pos] : -1;
+#pragma unroll
+      for (int k = 0; k + 1 < NGRAM_ORDERS; ++k) prev[j].d[k] = 0ull;
+#pragma unroll
+      for (int k = 0; k < NGRAM_ORDERS; ++k) earlier[k][j] = 0ull;
+    }
+    for (int t0 = 0; t0 < end; t0 += 64) {  // (prev carries D_k(p - 1) from one load to the next)
+      const int mine = t0 + lane < end ? (int32_t)row[t0 + lane] : -1;
+      const int n = end - t0 < 64 ? end - t0 : 64;
+      for (int i = 0; i < n; ++i) {
+        const int t = __builtin_amdgcn_readlane(mine, i);
+        const int p = t0 + i - s;  // the stream's position seen from the window: negative before it
+        unsigned long long above[WORDS];  // the positions of word j that lie behind p
+#pragma unroll
+        for (int j = 0; j < WORDS; ++j) {
+          const int q = p - 64 * j;
+          above[j] = q < 0 ? ~0ull : q >= 63 ? 0ull : ~0ull << (q + 1);
+        }
+        ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { earlier[k][j] |= d & above[j]; });
+      }
+    }
+#pragma unroll
+    for (int k = 0; k < NGRAM_ORDERS; ++k)
+#pragma unroll
+      for (int j = 0; j < WORDS; ++j) {
+        const int at = lane + 64 * j;
+        total[k] += __popcll(__ballot(at >= first && at >= k && s + at < end) & ~earlier[k][j]);
+      }
+    s += STRIDE;
+  } while (s + NGRAM_SEAM < len);
+  if (lane < NGRAM_ORDERS) {
+    int mine = 0;
+#pragma unroll
+    for (int k = 0; k < NGRAM_ORDERS; ++k) mine = lane == k && k < max_n ? total[k] : mine;
+    distinct[r * NGRAM_ORDERS + lane] = mine;
+  }
+}
+
+// ---- K44 -------------------------------------------------------------------------------------------------------------------------
+// The reference's rouge_n (evaluation/rouge.py rouge_n, in its order) from the counts: o = hit, P = o / |E|, R = o / |R| (0.0 where the
+// denominator is 0), F = 2.0 * ((P * R) / (P + R + 1e-8)).  One thread per (hypothesis (b, n), order k): the pair F of every present reference
+// (f32, rounded once) and the values against the one with the largest F, the lowest index among equals.
+__global__ __launch_bounds__(256) void rouge_n_scores_kernel(const int32_t* __restrict__ hit, const int32_t* __restrict__ hyp_distinct,
+                                                             const int32_t* __restrict__ ref_distinct, const int32_t* __restrict__ b_len,
+                                                             float* __restrict__ f_pair, double* __restrict__ f, double* __restrict__ p,
+                                                             double* __restrict__ r, int32_t* __restrict__ best_ref, const int64_t total,
+                                                             const int N, const int M, const int max_n) {
+#pragma clang fp contract(off)
+  const int64_t at = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (at >= total) return;
+  const int64_t h = at / NGRAM_ORDERS;
+  const int k = (int)(at - h * NGRAM_ORDERS);
+  const int64_t item = h / N;
+  const int e = hyp_distinct[at];
+  double best_f = 0.0, best_p = 0.0, best_r = 0.0;
+  int best = -1;
+  for (int m = 0; m < M; ++m) {
+    const int64_t pair = (h * M + m) * NGRAM_ORDERS + k;
+    if (k >= max_n || b_len[item * M + m] <= 0) {
+      f_pair[pair] = 0.0f;
+      continue;
+    }
+    const int o = hit[pair], d = ref_distinct[(item * M + m) * NGRAM_ORDERS + k];
+    const double pm = e == 0 ? 0.0 : (double)o / (double)e;
+    const double rm = d == 0 ? 0.0 : (double)o / (double)d;
+    const double fm = 2.0 * ((pm * rm) / (pm + rm + 1e-8));
+    f_pair[pair] = (float)fm;
+    if (best < 0 || fm > best_f) {
+      best = m;
+      best_f = fm;
+      best_p = pm;
+      best_r = rm;
+    }
+  }
+  f[at] = best_f;
+  p[at] = best_p;
+  r[at] = best_r;
+  best_ref[at] = best;
+}
+
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
+extern "C" int case_ngram_distinct(const int64_t* b, const int32_t* b_len, int32_t* distinct, int64_t rows, int64_t Tb, int32_t max_n,
+                                   case_stream_t stream) {
+  CASE_REQUIRE(b && b_len && distinct && rows > 0 && Tb > 0 && rows < (1ll << 31) && Tb < (1ll << 30) && max_n >= 1 && max_n <= NGRAM_ORDERS,
+               "case_ngram_distinct: bad argument");
+  const dim3 grid((unsigned)((rows + NGRAM_WAVES - 1) / NGRAM_WAVES)), block(64 * NGRAM_WAVES);
+  if (Tb <= 64)
+    hipLaunchKernelGGL(ngram_distinct_kernel<1>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
+  else if (Tb <= 128)
+    hipLaunchKernelGGL(ngram_distinct_kernel<2>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
+  else
+    hipLaunchKernelGGL(ngram_distinct_kernel<4>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
+  return case_check_launch("case_ngram_distinct");
+}
+
+extern "C" int case_rouge_n_scores(const int32_t* hit, const int32_t* hyp_distinct, const int32_t* ref_distinct, const int32_t* b_len,
+                                   float* f_pair, double* f, double* p, double* r, int32_t* best_ref, int64_t B, int64_t N, int64_t M,
+                                   int32_t max_n, case_stream_t stream) {
+  CASE_REQUIRE(hit && hyp_distinct && ref_distinct && b_len && f_pair && f && p && r && best_ref && B > 0 && N > 0 && M > 0 &&
+                   B < (1ll << 31) && N < (1ll << 24) && M < (1ll << 24) && B * N < (1ll << 31) && B * N * M < (1ll << 37) && max_n >= 1 &&
+                   max_n <= NGRAM_ORDERS,
+               "case_rouge_n_scores: bad argument");
+  const int64_t total = B * N * NGRAM_ORDERS;
+  hipLaunchKernelGGL(rouge_n_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, hit, hyp_distinct,
+                     ref_distinct, b_len, f_pair, f, p, r, best_ref, total, (int)N, (int)M, (int)max_n);
+  return case_check_launch("case_rouge_n_scores");
+}
+
 extern "C" int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* clip, int32_t* clip_any,
                                  int32_t* hit, int32_t* hit_any, int32_t* distinct, int64_t B, int64_t N, int64_t M, int64_t Ta, int64_t Tb,
                                  int32_t max_n, case_stream_t stream) {

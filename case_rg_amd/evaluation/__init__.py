@@ -1,12 +1,14 @@
 """Answer-quality metrics of the reference's evaluation scripts that the acceptance bar names (ROUGE-L): on the host over token strings
-(``rouge``), and on the device over token ids together with the consensus pick over a pool of candidates (``rouge_ids``); BLEU and the
+(``rouge``, with ROUGE-1 / ROUGE-2 beside it), and on the device over token ids together with the consensus pick over a pool of candidates
+(``rouge_ids``; ROUGE-N: ``rouge_n_ids``); BLEU and the
 n-gram overlap of an answer with its passages, on the host (``bleu``) and on the device (``ngram_ids``); METEOR with its exact stage on
 ids and one caller-provided class table, on the host (``meteor``) and on the device (``meteor_ids``); the TREC ranking metrics of the
 passage scores, on the host (``trec``) and on the device (``rank_ids``); the token-level counts of the supporting-token stage on the device
 (``token_ids``); answer attribution -- which passage each answer token was copied from -- on the device (``attribution``); the expected
 cost of a pool of candidates under the model's posterior and the minimum-risk training step built on it (``risk``)."""
-from .rouge import eval_rouge_l, lcs_length, rouge_l  # noqa: F401
+from .rouge import eval_rouge, eval_rouge_l, lcs_length, rouge_l, rouge_n  # noqa: F401
 from .rouge_ids import consensus, eval_rouge_l_ids, rouge_l_ids  # noqa: F401
+from .rouge_n_ids import eval_rouge_n_ids, rouge_n_ids  # noqa: F401
 from .bleu import eval_bleu, modified_precision, ngram_overlap, sentence_bleu  # noqa: F401
 from .ngram_ids import bleu_ids, eval_bleu_ids, ngram_overlap_ids  # noqa: F401
 from .meteor import best_meteor, count_chunks, eval_meteor, meteor_alignment, pair_meteor, sentence_meteor, stem_classes  # noqa: F401

@@ -63,7 +63,8 @@ def eval_rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
     return torch.where(out["ref_valid"], f, torch.zeros_like(f)).max(dim=1)[0] * 100
 
 
-CONSENSUS_METRICS = ("rouge_l", "bleu")
+CONSENSUS_METRICS = ("rouge_l", "bleu", "rouge_1", "rouge_2")
+_ROUGE_N_ORDER = {"rouge_1": 1, "rouge_2": 2}
 
 
 def consensus(candidates, specials, valid=None, weights=None, metric="rouge_l"):
@@ -73,7 +74,9 @@ def consensus(candidates, specials, valid=None, weights=None, metric="rouge_l"):
     The pick of item b maximises  sum_m w[b, m] F(candidate n as the hypothesis, m as the reference) / sum_m w[b, m]  over the valid
     candidates, the self term included, the lowest index on ties; an invalid candidate reads -inf and is never picked.
     ``metric="bleu"``: the utility F is sentence BLEU-4 with add-one smoothing (K34 + K35 on the pool against itself; unsmoothed sentence BLEU
-    is 0 for most short pairs and useless as a utility), and the dict carries ``pairwise_bleu`` f32 [B, N, N] instead of ``pairwise_f``."""
+    is 0 for most short pairs and useless as a utility), and the dict carries ``pairwise_bleu`` f32 [B, N, N] instead of ``pairwise_f``.
+    ``metric="rouge_1"`` / ``"rouge_2"``: the utility is the reference's ROUGE-N F (K34 on the pool against itself -- its ``distinct`` is
+    both |E| and |R|, a pool row fits K34 -- then K44), and the dict carries ``pairwise_rouge_1`` / ``pairwise_rouge_2`` instead."""
     bos, pad, eos, unk = specials
     if metric not in CONSENSUS_METRICS:
         raise ValueError("consensus: metric must be one of %s, not %r" % (CONSENSUS_METRICS, metric))
@@ -85,11 +88,15 @@ def consensus(candidates, specials, valid=None, weights=None, metric="rouge_l"):
     kept, count = _compact(candidates, bos, pad, eos, unk)
     if metric == "bleu":
         f = ops.bleu_scores(ops.ngram_counts(kept, count, kept, count, 4), count, count, 4, "add1")[0]
+    elif metric in _ROUGE_N_ORDER:
+        order = _ROUGE_N_ORDER[metric]
+        counts = ops.ngram_counts(kept, count, kept, count, order)
+        f = ops.rouge_n_scores(counts["hit"], counts["distinct"], counts["distinct"], count, order)["f_pair"][..., order - 1].contiguous()
     else:
         _, f = ops.lcs_pairs(kept, count, kept, count)
     weights = None if weights is None else weights.to(device=candidates.device, dtype=torch.float32)
     utility, index, answer = ops.consensus_pick(f, weights, valid, candidates)
-    return {"answer": answer, "consensus_index": index, "consensus_utility": utility, "pairwise_" + ("bleu" if metric == "bleu" else "f"): f}
+    return {"answer": answer, "consensus_index": index, "consensus_utility": utility, "pairwise_" + ("f" if metric == "rouge_l" else metric): f}
 
 
 def model_specials(vocab2id):
@@ -102,7 +109,7 @@ def consensus_answers(model, data, rank_of, pool="sample", candidates=None, vali
                       **sampling):
     """``do_consensus`` of the task models (CaSE, Masque): build the pool with the model's own decoders (or take ``candidates``), then
     ``consensus``.  ``rank_of(data)``: the model's passage ranking from its encode stages alone.  ``no_repeat_ngram`` goes to the pool's decoder
-    (None: the model's attribute); explicit candidates are taken as they are.  ``metric``: "rouge_l" or "bleu" (None: the model's
+    (None: the model's attribute); explicit candidates are taken as they are.  ``metric``: one of ``CONSENSUS_METRICS`` (None: the model's
     ``consensus_metric``), checked before anything is decoded."""
     if model.training:
         raise ValueError("do_consensus runs in eval mode: call model.eval() first")

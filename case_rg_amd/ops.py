@@ -2783,6 +2783,71 @@ def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
     return pair, bleu, bp
 
 
+# K43 / K44: the distinct k-grams of rows of any length and ROUGE-N from the counts
+def rouge_n_supported():
+    return bool(A.lib.case_abi_features() & A.FEAT_ROUGE_N)
+
+
+def _max_n(what, max_n):
+    if not isinstance(max_n, int) or isinstance(max_n, bool) or not 1 <= max_n <= NGRAM_MAX_ORDER:
+        raise ValueError("%s: max_n in 1..%d (got %r)" % (what, NGRAM_MAX_ORDER, max_n))
+
+
+def ngram_distinct(b, b_len, max_n=4):
+    """K43: b int64 [..., Tb] / b_len int32 [...] (front-packed rows and their lengths, as ``sentence_compact`` writes them; a length is
+    clamped to 0 .. Tb) -> distinct int32 [..., 4]: the number of distinct k-grams of every row for k = 1..4 on the last axis (0 above
+    ``max_n`` and for a row shorter than k).  Exact; Tb has no limit, the cost of a row grows with the SQUARE of its length (about
+    L^2 / 500 token steps).  Ids must lie in [0, 2^31) (not checked: compared on 32 bits)."""
+    if not torch.is_tensor(b) or b.dtype != torch.int64 or b.dim() < 2:
+        raise TypeError("ngram_distinct: b must be int64 [..., Tb]")
+    if not torch.is_tensor(b_len) or b_len.dtype != torch.int32 or tuple(b_len.shape) != tuple(b.shape[:-1]):
+        raise TypeError("ngram_distinct: b_len must be int32 %s for b %s" % (list(b.shape[:-1]), list(b.shape)))
+    if b_len.device != b.device:
+        raise ValueError("ngram_distinct: b is on %s, b_len on %s" % (b.device, b_len.device))
+    _max_n("ngram_distinct", max_n)
+    Tb = b.shape[-1]
+    rows = b_len.numel()
+    if rows < 1 or Tb < 1:
+        raise ValueError("ngram_distinct: at least one row and one position (got b %s)" % (list(b.shape),))
+    if not rouge_n_supported():
+        raise RuntimeError("ngram_distinct: this build of the library lacks K43 / K44 (CASE_FEAT_ROUGE_N)")
+    b, b_len = (t if t.is_contiguous() else t.contiguous() for t in (b, b_len))
+    distinct = torch.empty(*b_len.shape, NGRAM_MAX_ORDER, dtype=torch.int32, device=b.device)
+    A.call("case_ngram_distinct", _ptr(b), _ptr(b_len), _ptr(distinct), rows, Tb, max_n, _stream())
+    return distinct
+
+
+def rouge_n_scores(hit, hyp_distinct, ref_distinct, b_len, max_n=4):
+    """K44: hit int32 [B, N, M, 4] and hyp_distinct int32 [B, N, 4] (``ngram_counts``' ``hit`` and ``distinct``), ref_distinct int32 [B, M, 4]
+    (``ngram_distinct`` of the references), b_len int32 [B, M] (0: the reference is absent) -> dict(f_pair f32 [B, N, M, 4]: the reference's
+    ``rouge_n`` F of hypothesis n against reference m for the orders 1..4, f64 rounded once, 0 for an absent reference; f, p, r f64
+    [B, N, 4]: the values against the present reference with the largest F, the lowest index among equals; best_ref int32 [B, N, 4]: its
+    index, -1 without a present reference, and then f = p = r = 0).  The orders above ``max_n`` read 0 and best_ref -1."""
+    _max_n("rouge_n_scores", max_n)
+    tensors = (("hit", hit, 4), ("hyp_distinct", hyp_distinct, 3), ("ref_distinct", ref_distinct, 3), ("b_len", b_len, 2))
+    for name, t, dim in tensors:
+        if not torch.is_tensor(t) or t.dtype != torch.int32 or t.dim() != dim:
+            raise TypeError("rouge_n_scores: %s must be an int32 tensor of %d axes" % (name, dim))
+    B, N, M = hit.shape[:3]
+    if tuple(hit.shape) != (B, N, M, NGRAM_MAX_ORDER) or tuple(hyp_distinct.shape) != (B, N, NGRAM_MAX_ORDER) or \
+            tuple(ref_distinct.shape) != (B, M, NGRAM_MAX_ORDER) or tuple(b_len.shape) != (B, M):
+        raise TypeError("rouge_n_scores: hit [B, N, M, 4], hyp_distinct [B, N, 4], ref_distinct [B, M, 4] and b_len [B, M] (got %s, %s, %s, %s)"
+                        % tuple(list(t.shape) for _, t, _ in tensors))
+    if B < 1 or N < 1 or M < 1:
+        raise ValueError("rouge_n_scores: at least one item, one hypothesis and one reference slot (got hit %s)" % (list(hit.shape),))
+    if any(t.device != hit.device for _, t, _ in tensors):
+        raise ValueError("rouge_n_scores: the four tensors must be on one device")
+    if not rouge_n_supported():
+        raise RuntimeError("rouge_n_scores: this build of the library lacks K43 / K44 (CASE_FEAT_ROUGE_N)")
+    hit, hyp_distinct, ref_distinct, b_len = (t if t.is_contiguous() else t.contiguous() for t in (hit, hyp_distinct, ref_distinct, b_len))
+    new = lambda dtype: torch.empty(B, N, NGRAM_MAX_ORDER, dtype=dtype, device=hit.device)  # noqa: E731
+    out = dict(f_pair=torch.empty(B, N, M, NGRAM_MAX_ORDER, dtype=torch.float32, device=hit.device), f=new(torch.float64),
+               p=new(torch.float64), r=new(torch.float64), best_ref=new(torch.int32))
+    A.call("case_rouge_n_scores", _ptr(hit), _ptr(hyp_distinct), _ptr(ref_distinct), _ptr(b_len), _ptr(out["f_pair"]), _ptr(out["f"]),
+           _ptr(out["p"]), _ptr(out["r"]), _ptr(out["best_ref"]), B, N, M, max_n, _stream())
+    return out
+
+
 # K40: METEOR on token ids
 METEOR_MAX_T = 256
 

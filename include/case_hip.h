@@ -83,7 +83,9 @@ enum {
   CASE_FEAT_TOKEN_LABELS = 1u << 27,      /* K37 / K38 case_token_labels / case_token_select */
   CASE_FEAT_COPY_ATTRIBUTION = 1u << 28,  /* K39 case_copy_attribution */
   CASE_FEAT_METEOR = 1u << 29,            /* K40 case_meteor */
-  CASE_FEAT_RISK_TRAIN = 1u << 30         /* K41 / K42 case_pointer_head_score_stats / _bwd, case_sequence_risk */
+  CASE_FEAT_RISK_TRAIN = 1u << 30,        /* K41 / K42 case_pointer_head_score_stats / _bwd, case_sequence_risk */
+  CASE_FEAT_ROUGE_N = 1u << 31            /* K43 / K44 case_ngram_distinct / case_rouge_n_scores.  The LAST free bit of the 32-bit mask: the
+                                             next feature needs a second query (or a generation), not a 33rd bit */
 };
 uint32_t case_abi_features(void);
 const char* case_last_error(void);
@@ -837,6 +839,32 @@ int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, 
                       int32_t max_n, case_stream_t stream);
 int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t* a_len, const int32_t* b_len, float* bleu_pair,
                      double* bleu_any, double* bp, int64_t B, int64_t N, int64_t M, int32_t max_n, int32_t smoothing, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ROUGE-1 .. ROUGE-4 on token ids (CASE_FEAT_ROUGE_N; purely additive, generation 600 unchanged).  The metric is evaluation/Rouge.py:140-183
+ * (rouge_n), a SET measure: with E and R the distinct k-grams of the hypothesis and of the reference and o = |E & R|,
+ *     P = o / |E|,  R = o / |R|  (0.0 where the denominator is 0),  F = 2.0 * ((P * R) / (P + R + 1e-8)).
+ * K34 gives o (hit) and |E| (distinct); K43 gives |R| for rows of any length.
+ * K43 case_ngram_distinct: b int64 [rows, Tb] front-packed ids, b_len int32 [rows] (clamped to 0 .. Tb), ids compared on their low 32 bits
+ *   (the caller guarantees 0 <= id < 2^31, not checked); max_n in 1 .. 4.  distinct int32 [rows, 4]: entry k - 1 = the number of distinct
+ *   k-grams of the row's first b_len ids for k <= max_n; the orders above max_n read 0, and so does a row shorter than k.  Exact.
+ *   One wave per row, several rows per workgroup, no atomics, nothing read back: capturable, and two launches give the same bits.  Tb has no
+ *   limit: the row is counted in windows of 256 positions (64 / 128 for Tb <= 64 / 128) that overlap by 3, and every window is compared with
+ *   the whole row before it, so a row of L ids costs about L^2 / 500 token steps of wave-wide mask arithmetic -- quadratic in L.
+ *   On rows of at most 256 positions the result is K34's distinct[b, n, :] bit for bit.
+ * K44 case_rouge_n_scores: hit int32 [B, N, M, 4] and hyp_distinct int32 [B, N, 4] (K34's hit and distinct), ref_distinct int32 [B, M, 4]
+ *   (K43's, or K34's distinct when the references are the hypotheses), b_len int32 [B, M] (<= 0: the reference is absent).  For every order
+ *   k <= max_n (index k - 1 of the last axis), in f64 in the order above, without contraction:
+ *     f_pair[b, n, m, k] (f32, rounded once) = F of hypothesis n against reference m; 0 for an absent reference;
+ *     f, p, r [b, n, k] (f64) = F, P, R against the present reference with the largest F, the lowest index among equals;
+ *     best_ref[b, n, k] (int32) = that index; -1 without a present reference, and then f = p = r = 0.
+ *   The orders above max_n are not evaluated: f_pair, f, p, r read 0 and best_ref -1.
+ * ------------------------------------------------------------------------------------------- */
+int case_ngram_distinct(const int64_t* b, const int32_t* b_len, int32_t* distinct, int64_t rows, int64_t Tb, int32_t max_n,
+                        case_stream_t stream);
+int case_rouge_n_scores(const int32_t* hit, const int32_t* hyp_distinct, const int32_t* ref_distinct, const int32_t* b_len, float* f_pair,
+                        double* f, double* p, double* r, int32_t* best_ref, int64_t B, int64_t N, int64_t M, int32_t max_n,
+                        case_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
  * TREC ranking metrics of score rows (CASE_FEAT_RANK_METRICS; purely additive, generation 600 unchanged): what evaluation/Eval_Trec.py
