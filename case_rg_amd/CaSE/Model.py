@@ -13,7 +13,7 @@ from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, decode_rules_param, no_repeat_ngram_param, sampling_params
 from ..common.Utils import to_sentence, token_freq_table
-from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair, run_blocks
+from ..common.heads import block_stack, nll_mean, passage_bce, run_block_pair, run_blocks
 from ..evaluation.attribution import attribute_answers
 from ..evaluation.risk import MRT_DEFAULTS, minimum_risk_step
 from ..evaluation.rouge_ids import consensus_answers
@@ -55,10 +55,10 @@ class CaSETransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, groundtruth_index=None, additional_decoder_feature=None,
                 encode_weights=None, encode_masks=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None,
-                score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
+                score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False, loss_only=False):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
                          score_index, feature_of=lambda T: self._feature(additional_decoder_feature, T), no_repeat_ngram=no_repeat_ngram,
-                         decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
+                         decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head, loss_only=loss_only)
 
 
 class RelevantPassageSelection(nn.Module):
@@ -142,7 +142,7 @@ class ResponseGeneration(nn.Module):
 
     def action(self, query, passage, source_map, encode_query, encode_passage, passage_selection_result,
                span_extraction_result, output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0,
-               decode_rules=None, segments=None, score_grad_head=False):
+               decode_rules=None, segments=None, score_grad_head=False, loss_only=False):
         B = query.size(0)
         passage_score = passage_selection_result[0]
         token_score, query_rep, passage_rep = span_extraction_result
@@ -156,7 +156,8 @@ class ResponseGeneration(nn.Module):
                             additional_decoder_feature=answer_rep, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head,
+                            loss_only=loss_only)
 
 
 class CaSE(nn.Module):
@@ -260,11 +261,11 @@ class CaSE(nn.Module):
         token_label, token_weight = self._token_supervision(data)
         eq, ep, ps, se = self._encode_select_extract(data)
         loss_ps, loss_se = self._stage_losses(data, ps, se, token_label, token_weight)
-        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
-                                             encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
-                                             output=data['response'])
-        dist1, dist2 = rg[2]
-        return [loss_ps, loss_se, generation_nll(ops.add(dist1, dist2), data['response'])]
+        # the decoder's loss-only head: per-row NLL without a [rows, V] distribution where the fused head runs, the dense chain otherwise
+        rows = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                               encode_passage=ep, passage_selection_result=ps, span_extraction_result=se,
+                                               output=data['response'], loss_only=True)
+        return [loss_ps, loss_se, nll_mean(rows, data['response'])]
 
     def do_mrt(self, data, candidates=None, num_samples=None, alpha=None, with_reference=None, dedup=None, mle_weight=None, details=False,
                **sampling):

@@ -8,7 +8,7 @@ from ..common.Constants import BOS_WORD, EOS_WORD, UNK_WORD
 from ..common.Interaction import Interaction
 from ..common.TransformerSeqEncoderDecoder import PointerDecoderCore, TransformerSeqEncoder, decode_rules_param, no_repeat_ngram_param, sampling_params
 from ..common.Utils import to_sentence
-from ..common.heads import block_stack, generation_nll, passage_bce, run_block_pair
+from ..common.heads import block_stack, nll_mean, passage_bce, run_block_pair
 from ..evaluation.attribution import attribute_answers
 from ..evaluation.risk import MRT_DEFAULTS, minimum_risk_step
 from ..evaluation.rouge_ids import consensus_answers
@@ -38,9 +38,10 @@ class MasqueTransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_map, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
+                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False, loss_only=False):
         return self._run(encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head,
+                         loss_only=loss_only)
 
 
 class PassageSelection(nn.Module):
@@ -87,7 +88,7 @@ class ResponseGeneration(nn.Module):
 
     def action(self, query, passage, source_map, encode_query=None, encode_passage=None, passage_selection_result=None,
                output=None, max_target_length=None, beam_width=None, sampling=None, score_index=None, no_repeat_ngram=0, decode_rules=None, segments=None,
-               score_grad_head=False):
+               score_grad_head=False, loss_only=False):
         if encode_query is None:
             encode_query = self.query_encoder(query)[0][:, :, -1]
         if encode_passage is None:
@@ -102,7 +103,8 @@ class ResponseGeneration(nn.Module):
         return self.decoder([query_rep, passage_rep], self.BOS, self.UNK, source_map, groundtruth_index=output,
                             max_target_length=max_target_length, encode_masks=[query.ne(0), passage.ne(0)],
                             encode_weights=[prior_q, prior_p], beam_width=beam_width, sampling=sampling, score_index=score_index,
-                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
+                            no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head,
+                            loss_only=loss_only)
 
 
 class Masque(nn.Module):
@@ -152,9 +154,9 @@ class Masque(nn.Module):
 
     def do_train(self, data):
         eq, ep, ps = self._encode_select(data)
-        rg = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
-                                             encode_passage=ep, passage_selection_result=ps, output=data['response'])
-        return self._stage_losses(data, ps) + [generation_nll(rg[2], data['response'])]
+        rows = self.response_generation.action(data['query'], data['passage'], data['source_map'], encode_query=eq,
+                                               encode_passage=ep, passage_selection_result=ps, output=data['response'], loss_only=True)
+        return self._stage_losses(data, ps) + [nll_mean(rows, data['response'])]
 
     @staticmethod
     def _stage_losses(data, ps):

@@ -169,6 +169,8 @@ SIGNATURES = {
     "case_pointer_head_score_stats": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64, ptr, ptr, ptr, i64, i64, i64, ptr],
     "case_pointer_head_score_bwd": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64] + [ptr] * 6 + [i64, i64, i64, ptr],
     "case_sequence_risk": [ptr] * 4 + [f64] + [ptr] * 3 + [i64, i64, i64, ptr],
+    "case_pointer_head_loss": [ptr, i64, ptr, ptr, i64, ptr, ptr, i32, ptr, i64, ptr, ptr, ptr, ptr, i64, i64, i64, ptr],
+    "case_pointer_head_loss_bwd": [ptr, i64, ptr, ptr, i64, ptr, ptr, i32, ptr, i64, ptr, ptr, ptr, ptr, i32, ptr, ptr, i64, i64, i64, ptr],
     "case_gemm_ln": [C.POINTER(GemmDesc), ptr, ptr, ptr, f32, ptr, ptr, ptr, ptr, ptr, ptr],
     "case_optim_sumsq": [ptr, ptr, i64, ptr, ptr, ptr],
     "case_optim_adam_ema": [ptr, ptr, i64, ptr, f32, f64, f64, f64, f64, ptr, ptr],
@@ -176,6 +178,10 @@ SIGNATURES = {
     "case_interaction_supported": [C.POINTER(InteractionDesc)],
     "case_interaction_fwd": [C.POINTER(InteractionDesc), ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr, ptr],
 }
+
+# Entry points added after the 32-bit feature mask filled up: an older build of the same ABI generation may lack them, so they are bound
+# where the library exports them and asked for by name (``has``) instead of by feature bit
+OPTIONAL = ("case_pointer_head_loss", "case_pointer_head_loss_bwd")
 
 
 def _load():
@@ -190,6 +196,8 @@ def _load():
         raise ImportError("case_rg_amd: %s is ABI generation %d, this package binds %d -- rebuild it (make -C case_rg_amd/csrc)"
                           % (LIB_PATH, lib.case_version(), ABI_VERSION))
     for name, args in SIGNATURES.items():
+        if name in OPTIONAL and not hasattr(lib, name):
+            continue
         fn = getattr(lib, name)  # AttributeError if the .so does not export a declared symbol
         fn.argtypes = args
         fn.restype = C.c_int
@@ -224,6 +232,11 @@ def _load():
 
 
 lib = _load()
+
+
+def has(name):
+    """Whether the loaded library exports ``name`` (for the OPTIONAL entry points; the feature mask covers the rest)."""
+    return hasattr(lib, name)
 
 
 def check(code, what):

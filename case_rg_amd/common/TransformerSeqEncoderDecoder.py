@@ -628,10 +628,11 @@ class PointerDecoderCore(nn.Module):
         return out
 
     def _run(self, encode_memories, encode_masks, encode_weights, source_map, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
+             score_index, feature_of=None, no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False, loss_only=False):
         """What the three ``forward``s share: score / train / beam / sample / greedy.  ``feature_of(T)``: the decoder feature for T positions
         (CaSE's answer representation), or None.  ``no_repeat_ngram`` (K32) and ``decode_rules`` (what ``decode_rules_param`` returned: min_length,
-        banned ids, the beam length penalty) apply to the three decoding modes only."""
+        banned ids, the beam length penalty) apply to the three decoding modes only.  ``loss_only`` (the training branch; ``do_train`` sets it):
+        the result is the per-row NLL of ``groundtruth_index``, f32 [B * T] (``_train_nll``), instead of (dec_out, gen, dist, index)."""
         B, dev = source_map.size(0), encode_memories[0].device
         source_map = self._sorted(source_map)
         mems = [m.reshape(B, -1, self.hidden_size) for m in encode_memories]
@@ -643,6 +644,8 @@ class PointerDecoderCore(nn.Module):
         if self.training and groundtruth_index is not None:
             dec_ids = torch.cat([self._bos(B, BOS, dev), groundtruth_index[:, :-1]], dim=-1)
             feat = None if feature_of is None else feature_of(dec_ids.size(1))
+            if loss_only:
+                return self._train_nll(*self._run_prefix(dec_ids, mems, valid, weights, feat), feat, source_map, groundtruth_index)
             dec_out, gen, dist = self._head(*self._run_prefix(dec_ids, mems, valid, weights, feat), feat, source_map)
             return dec_out, gen, dist, groundtruth_index
         if self.training:
@@ -699,6 +702,28 @@ class PointerDecoderCore(nn.Module):
         d1, d2 = self._mix(dec_out, ctxs, gen, copies, source_map)
         return dec_out, gen, ((d1, d2) if self.training and self.train_returns_pair else ops.add(d1, d2))
 
+    def _train_nll(self, dec_in, x, ctxs, copies, feat, source_map, target):
+        """The training head when only the loss is wanted: -log(p(target) + 1e-8) per (item, position) row, f32 [B * T], 0 where the target
+        is PAD.  Where ``ops.train_head_supported`` (CASE_TRAIN_HEAD=auto, a device-sorted source map, <= 4 memories, CASE_POINTER_SCORE not
+        off, a library with the loss-form kernels) it is the generator's first Linear -- the SAME dropout site, drawn at the same point of
+        the counter stream, as ``_generate`` -- the mixing logits and ``ops.train_head_nll``: no [rows, V] probability tensor exists.
+        Otherwise the dense chain of ``_head`` and a gather."""
+        V, H = self.tgt_vocab_size, self.hidden_size
+        if not ops.train_head_supported(source_map, len(ctxs)):
+            _, _, dist = self._head(dec_in, x, ctxs, copies, feat, source_map)
+            dist = ops.add(*dist) if isinstance(dist, tuple) else dist
+            return ops.nll_rows(dist.reshape(-1, V), target.reshape(-1))
+        B, T = target.shape
+        dec_out, gen_in = self._head_parts(dec_in, x, feat)
+        h = ops.linear(gen_in, self.gen[0].weight, self.gen[0].bias, p_drop=config.drop_p(self.gen_dropout, self.training))
+        parts = [dec_out] + ctxs
+        if ops.linear_skinny_supported(parts, self.mix.weight, with_grad=True):
+            mix_logits = ops.linear_skinny_grad(parts, self.mix.weight, self.mix.bias)
+        else:
+            mix_logits = ops.linear(torch.cat(parts, dim=-1), self.mix.weight, self.mix.bias, out_dtype=torch.float32)
+        return ops.train_head_nll(h.reshape(B * T, H), self.gen[-2].weight, mix_logits.reshape(B * T, -1), source_map, T,
+                                  [c.reshape(B * T, -1) for c in copies], target.reshape(-1))
+
     def _generate(self, gen_in, hidden_drop):
         """gen = softmax(W_v (drop(W_h x + b)))  -- f32 logits and probabilities (K10)."""
         h = ops.linear(gen_in, self.gen[0].weight, self.gen[0].bias, p_drop=config.drop_p(hidden_drop, self.training))
@@ -745,8 +770,9 @@ class TransformerSeqDecoder(PointerDecoderCore):
 
     def forward(self, encode_memories, BOS, UNK, source_maps, encode_masks=None, encode_weights=None,
                 groundtruth_index=None, init_decoder_state=None, max_target_length=None, beam_width=None, sampling=None, score_index=None,
-                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False):
+                no_repeat_ngram=0, decode_rules=None, segments=None, score_grad_head=False, loss_only=False):
         if isinstance(source_maps, (list, tuple)):
             source_maps = torch.cat(source_maps, dim=-2 if source_maps[0].dim() == 3 else -1)
         return self._run(encode_memories, encode_masks, encode_weights, source_maps, BOS, groundtruth_index, max_target_length, beam_width, sampling,
-                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head)
+                         score_index, no_repeat_ngram=no_repeat_ngram, decode_rules=decode_rules, segments=segments, score_grad_head=score_grad_head,
+                         loss_only=loss_only)

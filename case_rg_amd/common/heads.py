@@ -75,6 +75,11 @@ def generation_nll(dist, response):
     """mean over non-pad targets of -log(dist[target] + 1e-8)  (CaSE/Model.py:306, Masque/Model.py:239).
     The gather and its sparse gradient are kernels (K12); the final mean over B*T numbers is glue."""
     V = dist.size(-1)
-    rows = ops.nll_rows(dist.reshape(-1, V), response.reshape(-1))
+    return nll_mean(ops.nll_rows(dist.reshape(-1, V), response.reshape(-1)), response)
+
+
+def nll_mean(rows, response):
+    """``generation_nll``'s reduction of per-row losses f32 [B * T] (0 on PAD rows): their sum over the count of non-pad targets, clamped to 1
+    (glue).  ``do_train`` feeds it the rows of the decoder's loss-only head."""
     count = response.ne(0).sum().clamp(min=1)
     return (rows.sum() / count).unsqueeze(0)

@@ -1147,17 +1147,29 @@ struct ScoreArgs {
   float* prob;              // [R]
   float* ptr;               // [R] or null: the pointer part of prob
   float* stats;             // [R, 2] or null: the row's final (max, sum) of the online softmax (case_pointer_head_score_stats)
+  float* nll;               // [R] the loss form only: -log(prob + 1e-8), 0 for a PAD row
   int64_t V, S, rows_per_source, pad;
+  int64_t ld;               // the loss form only: floats between two logits rows (>= V; K29 itself reads rows V apart)
   int nmem;
 };
 
 typedef float ps_f32x4 __attribute__((ext_vector_type(4)));
+typedef float ps_f32x4u __attribute__((ext_vector_type(4), aligned(4)));  // a 16-byte access on a 4-byte boundary
 #ifndef CASE_STREAM_DEFAULT_POLICY
 #define PS_LOAD1(P) __builtin_nontemporal_load(P)
 #define PS_LOAD4(P) __builtin_nontemporal_load(reinterpret_cast<const ps_f32x4*>(P))
 #else
 #define PS_LOAD1(P) (*(P))
 #define PS_LOAD4(P) (*reinterpret_cast<const ps_f32x4*>(P))
+#endif
+// The loss form (the training head) reads its logits with the DEFAULT policy: K41's loss form reads the same 157 MB again a few launches
+// later, and they fit the Infinity Cache.  -DCASE_LOSS_STREAM_NT: non-temporal as K29 (A/B; DESIGN 9.7 has the pair of timings).
+#ifdef CASE_LOSS_STREAM_NT
+#define PL_LOAD1(P) __builtin_nontemporal_load(P)
+#define PL_LOAD4(P) __builtin_nontemporal_load(reinterpret_cast<const ps_f32x4u*>(P))
+#else
+#define PL_LOAD1(P) (*(P))
+#define PL_LOAD4(P) (*reinterpret_cast<const ps_f32x4u*>(P))
 #endif
 
 // (m, s) <- (m, s) (+) (om, os) with s = sum exp(x - m); an empty side is (-inf, 0)
@@ -1168,6 +1180,13 @@ __device__ __forceinline__ void ps_merge(float& m, float& s, const float om, con
   m = M;
 }
 
+// LOSS: the head of the TRAINING step (case_pointer_head_loss).  The same body with three differences.  Row r starts at logits + r * ld
+// (ld >= V: the vocabulary GEMM writes rows padded to its 256-wide tiles; columns [V, ld) are never read).  nll[r] = -log(prob + 1e-8),
+// 0 for a PAD row, is written beside prob.  And the row is split over the threads as K29 splits row r of a CONTIGUOUS [R, V] buffer on a
+// 16-byte boundary -- (-r V) mod 4 peeled floats, then groups of four -- whatever ld is, so prob / copy / stats carry K29's bits for the
+// same logits; where that split is out of phase with the padded row (V = 30 522: every odd row, by 8 bytes) the 16-byte loads are
+// unaligned, which costs one more cache line per wave and load.
+template <bool LOSS>
 __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const ScoreArgs a) {
   __shared__ float red_m[PS_THREADS / 64], red_s[PS_THREADS / 64];
   const int64_t r = blockIdx.x, V = a.V;
@@ -1179,19 +1198,28 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const Sc
       a.prob[r] = is_pad ? 1.f : 0.f;
       if (a.ptr) a.ptr[r] = 0.f;
       if (a.stats) a.stats[2 * r] = a.stats[2 * r + 1] = 0.f;
+      if constexpr (LOSS) {
+        float p0 = 0.f;
+        asm volatile("" : "+v"(p0));  // (opaque: logf of a constant would be folded with the host's libm, whose last bit can differ)
+        a.nll[r] = is_pad ? 0.f : -logf(p0 + 1e-8f);
+      }
     }
     return;
   }
-  const float* lg = a.logits + r * V;
-  int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
+  const float* lg = a.logits + r * (LOSS ? a.ld : V);
+  int64_t head;
+  if constexpr (LOSS) head = (-(r * V)) & 3;
+  else head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
   if (head > V) head = V;
   const int64_t n4 = (V - head) >> 2, tail = head + 4 * n4;
   float m = -INFINITY, s = 0.f;
-  if (tid < head) ps_merge(m, s, PS_LOAD1(lg + tid), 1.f);
+  if (tid < head) ps_merge(m, s, LOSS ? PL_LOAD1(lg + tid) : PS_LOAD1(lg + tid), 1.f);
   const float* body = lg + head;
 #pragma unroll 2
   for (int64_t i = tid; i < n4; i += PS_THREADS) {
-    const ps_f32x4 x = PS_LOAD4(body + 4 * i);
+    ps_f32x4 x;
+    if constexpr (LOSS) x = PL_LOAD4(body + 4 * i);
+    else x = PS_LOAD4(body + 4 * i);
     const float m4 = fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3]));
     if (m4 > m) {
       s *= __expf(m - m4);  // (m = -inf: s = 0 stays 0)
@@ -1199,7 +1227,7 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const Sc
     }
     s += (__expf(x[0] - m) + __expf(x[1] - m)) + (__expf(x[2] - m) + __expf(x[3] - m));
   }
-  if (tail + tid < V) ps_merge(m, s, PS_LOAD1(lg + tail + tid), 1.f);
+  if (tail + tid < V) ps_merge(m, s, LOSS ? PL_LOAD1(lg + tail + tid) : PS_LOAD1(lg + tail + tid), 1.f);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float om = __shfl_xor(m, o, 64), os = __shfl_xor(s, o, 64);
@@ -1259,12 +1287,14 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_kernel(const Sc
   }
   acc = wave_sum(acc);
   if (lane == 0) {
-    a.prob[r] = pm[0] * gen_y + acc;
+    const float p = pm[0] * gen_y + acc;
+    a.prob[r] = p;
     if (a.ptr) a.ptr[r] = acc;
     if (a.stats) {
       a.stats[2 * r] = m;
       a.stats[2 * r + 1] = s;
     }
+    if constexpr (LOSS) a.nll[r] = -logf(p + 1e-8f);
   }
 }
 
@@ -1286,8 +1316,9 @@ struct ScoreBwdArgs {
   const int64_t* targets;   // [R]
   const float* stats;       // [R, 2] the forward's (max, sum)
   const float* prob;        // [R] the forward's output
-  const float* g;           // [R] dL / dprob
-  float* d_logits;          // [R, V]
+  const float* g;           // [R] dL / dprob; the loss form: dL / dnll
+  void* d_logits;           // [R, V] f32; the loss form: [R, ld] f32 or bf16
+  int64_t ld;               // the loss form only: elements between two rows of logits and of d_logits (>= V, a multiple of 8)
   float* d_mix;             // [R, 1 + nmem]
   float* d_copy[PH_MAX_MEM];  // [R, len_k]
   int64_t V, S, rows_per_source, pad;
@@ -1307,6 +1338,21 @@ __device__ __forceinline__ int ps_locate(const ScoreBwdArgs& a, int64_t& pos) {
   return k;
 }
 
+// LOSS: the backward of the TRAINING head (case_pointer_head_loss_bwd).  The upstream gradient is that of nll = -log(prob + 1e-8), so
+// the kernel forms dL / dprob = -g / (prob + 1e-8) itself; logits and d_logits rows lie ld apart (a multiple of 8 elements on 16-byte
+// bases, so every row is 16-byte aligned and nothing is peeled in front); d_logits is stored in the operand dtype of the two GEMMs that
+// read it next -- OutT = bf16: the f32 value rounded once to nearest even, 8 elements per 16-byte store -- and the pad columns [V, ld)
+// are WRITTEN as zeros: the dX GEMM reduces over them.  The group of 8 that holds column V is computed element by element and stored
+// whole.  The logits are read with the default policy, as the forward reads them (measured equal to non-temporal: -DCASE_LOSS_STREAM_NT).
+template <typename OutT>
+__device__ __forceinline__ void ps_store8(OutT* p, const float (&d)[8]);
+template <> __device__ __forceinline__ void ps_store8<float>(float* p, const float (&d)[8]) {
+  *reinterpret_cast<ps_f32x4*>(p) = ps_f32x4{d[0], d[1], d[2], d[3]};
+  *reinterpret_cast<ps_f32x4*>(p + 4) = ps_f32x4{d[4], d[5], d[6], d[7]};
+}
+template <> __device__ __forceinline__ void ps_store8<bf16_t>(bf16_t* p, const float (&d)[8]) { Vec16<bf16_t>::store(p, d); }
+
+template <typename OutT, bool LOSS>
 __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_bwd_kernel(const ScoreBwdArgs a) {
   __shared__ float red_c[PS_THREADS / 64][PH_MAX_MEM];
   const int64_t r = blockIdx.x, V = a.V, S = a.S;
@@ -1314,9 +1360,9 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_bwd_kernel(cons
   const int64_t y = a.targets[r];
   const bool is_pad = a.pad >= 0 && y == a.pad;
   const bool scored = !(is_pad || y < 0 || y >= V);  // (uniform over the workgroup)
-  const float* lg = a.logits + r * V;
-  float* dl = a.d_logits + r * V;
-  const float gr = scored ? a.g[r] : 0.f;
+  const float* lg = a.logits + r * (LOSS ? a.ld : V);
+  OutT* dl = reinterpret_cast<OutT*>(a.d_logits) + r * (LOSS ? a.ld : V);
+  const float gr = !scored ? 0.f : LOSS ? -a.g[r] / (a.prob[r] + 1e-8f) : a.g[r];
   // the mixing probabilities, as in K29
   float pm[1 + PH_MAX_MEM];
   {
@@ -1353,7 +1399,12 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_bwd_kernel(cons
   }
   if (!scored) {  // zeros everywhere (d_copy is done)
     if (tid <= a.nmem) a.d_mix[r * (a.nmem + 1) + tid] = 0.f;
-    for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = 0.f;
+    if constexpr (LOSS) {
+      const float zero[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+      for (int64_t v0 = 8 * (int64_t)tid; v0 < a.ld; v0 += 8 * PS_THREADS) ps_store8<OutT>(dl + v0, zero);
+    } else {
+      for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = 0.f;
+    }
     return;
   }
 #pragma unroll
@@ -1379,25 +1430,48 @@ __global__ __launch_bounds__(PS_THREADS) void pointer_head_score_bwd_kernel(cons
   }
   // the pass over V
   const float coef = gr * pm[0] * gen_y;
-  if (((reinterpret_cast<uintptr_t>(lg) ^ reinterpret_cast<uintptr_t>(dl)) & 15u) != 0) {  // rows out of phase: 4-byte accesses
-    for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = coef * ((v == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + v) - m) / s);
-    return;
-  }
-  int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
-  if (head > V) head = V;
-  const int64_t n4 = (V - head) >> 2, tail = head + 4 * n4;
-  if (tid < head) dl[tid] = coef * ((tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tid) - m) / s);
-  const float* body = lg + head;
+  if constexpr (LOSS) {
 #pragma unroll 2
-  for (int64_t i = tid; i < n4; i += PS_THREADS) {
-    const ps_f32x4 x = PS_LOAD4(body + 4 * i);
-    const int64_t v0 = head + 4 * i;
-    ps_f32x4 d;
+    for (int64_t v0 = 8 * (int64_t)tid; v0 < a.ld; v0 += 8 * PS_THREADS) {
+      float d[8];
+      if (v0 + 8 <= V) {
+#ifdef CASE_LOSS_STREAM_NT
+        const ps_f32x4 x0 = PS_LOAD4(lg + v0), x1 = PS_LOAD4(lg + v0 + 4);
+#else
+        const ps_f32x4 x0 = *reinterpret_cast<const ps_f32x4*>(lg + v0), x1 = *reinterpret_cast<const ps_f32x4*>(lg + v0 + 4);
+#endif
 #pragma unroll
-    for (int e = 0; e < 4; ++e) d[e] = coef * ((v0 + e == y ? 1.f : 0.f) - __expf(x[e] - m) / s);
-    *reinterpret_cast<ps_f32x4*>(dl + v0) = d;
+        for (int e = 0; e < 4; ++e) {
+          d[e] = coef * ((v0 + e == y ? 1.f : 0.f) - __expf(x0[e] - m) / s);
+          d[4 + e] = coef * ((v0 + 4 + e == y ? 1.f : 0.f) - __expf(x1[e] - m) / s);
+        }
+      } else {  // the group that holds column V, and the pad behind it: nothing at or behind column V is read
+#pragma unroll
+        for (int e = 0; e < 8; ++e) d[e] = v0 + e < V ? coef * ((v0 + e == y ? 1.f : 0.f) - __expf(lg[v0 + e] - m) / s) : 0.f;
+      }
+      ps_store8<OutT>(dl + v0, d);
+    }
+  } else {  // K41 itself: f32 rows V apart at any phase
+    if (((reinterpret_cast<uintptr_t>(lg) ^ reinterpret_cast<uintptr_t>(dl)) & 15u) != 0) {  // rows out of phase: 4-byte accesses
+      for (int64_t v = tid; v < V; v += PS_THREADS) dl[v] = coef * ((v == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + v) - m) / s);
+      return;
+    }
+    int64_t head = (int64_t)(((16u - (uint32_t)(reinterpret_cast<uintptr_t>(lg) & 15u)) & 15u) >> 2);  // floats in front of the first 16-byte boundary
+    if (head > V) head = V;
+    const int64_t n4 = (V - head) >> 2, tail = head + 4 * n4;
+    if (tid < head) dl[tid] = coef * ((tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tid) - m) / s);
+    const float* body = lg + head;
+#pragma unroll 2
+    for (int64_t i = tid; i < n4; i += PS_THREADS) {
+      const ps_f32x4 x = PS_LOAD4(body + 4 * i);
+      const int64_t v0 = head + 4 * i;
+      ps_f32x4 d;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) d[e] = coef * ((v0 + e == y ? 1.f : 0.f) - __expf(x[e] - m) / s);
+      *reinterpret_cast<ps_f32x4*>(dl + v0) = d;
+    }
+    if (tail + tid < V) dl[tail + tid] = coef * ((tail + tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tail + tid) - m) / s);
   }
-  if (tail + tid < V) dl[tail + tid] = coef * ((tail + tid == y ? 1.f : 0.f) - __expf(PS_LOAD1(lg + tail + tid) - m) / s);
 }
 
 // ---- K11 ---------------------------------------------------------------------------------------
@@ -2091,7 +2165,8 @@ extern "C" int case_row_rules(float* dist, const uint8_t* ended, int64_t R, int6
 
 static int pointer_head_score_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
                                      const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
-                                     float* prob, float* copy, float* stats, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+                                     float* prob, float* copy, float* stats, int64_t R, int64_t V, int64_t S, case_stream_t stream,
+                                     float* nll = nullptr, int64_t ld = 0) {
   CASE_REQUIRE(targets && prob, "%s: bad argument", who);
   CASE_REQUIRE(rows_per_source >= 1 && R % rows_per_source == 0, "%s: %lld rows are no multiple of rows_per_source %lld", who, (long long)R,
                (long long)rows_per_source);
@@ -2102,9 +2177,12 @@ static int pointer_head_score_launch(const char* who, const float* logits, const
   a.prob = prob;
   a.ptr = copy;
   a.stats = stats;
+  a.nll = nll;
+  a.ld = ld;
   a.rows_per_source = rows_per_source;
   a.pad = pad;
-  hipLaunchKernelGGL(pointer_head_score_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
+  if (nll) hipLaunchKernelGGL(pointer_head_score_kernel<true>, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL(pointer_head_score_kernel<false>, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
   return case_check_launch(who);
 }
 
@@ -2122,11 +2200,11 @@ extern "C" int case_pointer_head_score_stats(const float* logits, const float* m
                                    copy, stats, R, V, S, stream);
 }
 
-extern "C" int case_pointer_head_score_bwd(const float* logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
-                                           const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
-                                           const float* stats, const float* prob, const float* g, float* d_logits, float* d_mix,
-                                           float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
-  const char* who = "case_pointer_head_score_bwd";
+// K41 and its loss form: ld < 0 = K41 itself (f32 rows V apart); else the loss form with rows ld apart and d_logits of `d_dtype`
+static int pointer_head_score_bwd_launch(const char* who, const float* logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                                         const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                         const float* stats, const float* prob, const float* g, void* d_logits, float* d_mix,
+                                         float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream, int64_t ld, int32_t d_dtype) {
   CASE_REQUIRE(logits && mix_logits && ids && copies && lens && targets && stats && prob && g && d_logits && d_mix && d_copies && R > 0 && V > 0 &&
                    S > 0 && nmem >= 1 && R < (1ll << 31),
                "%s: bad argument", who);
@@ -2158,8 +2236,46 @@ extern "C" int case_pointer_head_score_bwd(const float* logits, const float* mix
   a.rows_per_source = rows_per_source;
   a.pad = pad;
   a.nmem = nmem;
-  hipLaunchKernelGGL(pointer_head_score_bwd_kernel, dim3((unsigned)R), dim3(PS_THREADS), 0, (hipStream_t)stream, a);
+  a.ld = ld;
+  const dim3 grid((unsigned)R), block(PS_THREADS);
+  if (ld < 0) hipLaunchKernelGGL((pointer_head_score_bwd_kernel<float, false>), grid, block, 0, (hipStream_t)stream, a);
+  else if (d_dtype == CASE_BF16) hipLaunchKernelGGL((pointer_head_score_bwd_kernel<bf16_t, true>), grid, block, 0, (hipStream_t)stream, a);
+  else hipLaunchKernelGGL((pointer_head_score_bwd_kernel<float, true>), grid, block, 0, (hipStream_t)stream, a);
   return case_check_launch(who);
+}
+
+extern "C" int case_pointer_head_score_bwd(const float* logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                                           const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                           const float* stats, const float* prob, const float* g, float* d_logits, float* d_mix,
+                                           float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  return pointer_head_score_bwd_launch("case_pointer_head_score_bwd", logits, mix_logits, ids, rows_per_source, copies, lens, nmem, targets, pad, stats,
+                                       prob, g, d_logits, d_mix, d_copies, R, V, S, stream, -1, CASE_F32);
+}
+
+// the training head: K29 with row statistics plus the per-row loss, over logits rows `ld_logits` apart
+extern "C" int case_pointer_head_loss(const float* logits, int64_t ld_logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                                      const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                      float* prob, float* copy, float* stats, float* nll, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  const char* who = "case_pointer_head_loss";
+  CASE_REQUIRE(stats && nll, "%s: bad argument", who);
+  CASE_REQUIRE(ld_logits >= V && ld_logits % 4 == 0 && (uintptr_t)logits % 16 == 0,
+               "%s: logits rows must lie ld_logits >= V floats apart, a multiple of 4, on a 16-byte base (got ld %lld, V %lld)", who,
+               (long long)ld_logits, (long long)V);
+  return pointer_head_score_launch(who, logits, mix_logits, keys, rows_per_source, copies, lens, nmem, targets, pad, prob, copy, stats, R, V, S, stream,
+                                   nll, ld_logits);
+}
+
+extern "C" int case_pointer_head_loss_bwd(const float* logits, int64_t ld_logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                                          const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                                          const float* stats, const float* prob, const float* g_nll, void* d_logits, int32_t d_dtype, float* d_mix,
+                                          float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream) {
+  const char* who = "case_pointer_head_loss_bwd";
+  CASE_REQUIRE(d_dtype == CASE_F32 || d_dtype == CASE_BF16, "%s: d_logits is f32 or bf16 (got dtype %d)", who, (int)d_dtype);
+  CASE_REQUIRE(ld_logits >= V && ld_logits % 8 == 0 && (uintptr_t)logits % 16 == 0 && (uintptr_t)d_logits % 16 == 0,
+               "%s: logits / d_logits rows must lie ld_logits >= V elements apart, a multiple of 8, on 16-byte bases (got ld %lld, V %lld)", who,
+               (long long)ld_logits, (long long)V);
+  return pointer_head_score_bwd_launch(who, logits, mix_logits, ids, rows_per_source, copies, lens, nmem, targets, pad, stats, prob, g_nll, d_logits,
+                                       d_mix, d_copies, R, V, S, stream, ld_logits, d_dtype);
 }
 
 extern "C" int case_copy_scatter_fwd(const int64_t* src, const float* w, float* dist, int64_t B, int64_t T, int64_t S,

@@ -91,6 +91,56 @@ def cast_param(p, dtype):
     return paramcache.derived(owners, tag, lambda: cast(p.detach(), dtype))
 
 
+def rowpad_rows(rows, multiple):
+    return -(-int(rows) // int(multiple)) * int(multiple)
+
+
+def rowpad_wanted(p):
+    """The row multiple a caller of ``cast_param_rowpad`` has asked for on this parameter (0: none) -- FusedAdam then keeps its persistent
+    operand copy of it inside a padded buffer (``new_rowpad_copy``)."""
+    return int(getattr(p, "_case_rowpad_multiple", 0))
+
+
+def new_rowpad_copy(p, dtype, multiple):
+    """An UNFILLED operand copy of the 2-D parameter ``p`` [V, K] as the [:V] prefix view of a zero-initialised [Vp, K] buffer, Vp = V rounded
+    up to ``multiple``; the view carries the buffer as ``_case_rowpad_buf``.  A writer of the copy (case_cast, the optimizer kernel) touches the
+    first V K elements only, so rows [V, Vp) stay zero for the life of the buffer."""
+    buf = torch.zeros(rowpad_rows(p.shape[0], multiple), p.shape[1], dtype=dtype, device=p.device)
+    low = buf[:p.shape[0]]
+    low._case_rowpad_buf = buf
+    return low
+
+
+def cast_param_rowpad(p, dtype, multiple=256):
+    """2-D parameter [V, K] -> its operand copy of ``dtype`` with the rows padded to a multiple of ``multiple``: [Vp, K], rows [V, Vp) zero
+    (a GEMM over it runs on whole tiles; the columns / reduction terms it adds are exact zeros).  Kept in paramcache under its own tag and
+    dropped with every other copy when the parameters are rewritten.  Where the live cast copy of ``p`` (``cast_param``'s entry: FusedAdam
+    installs its persistent one after every step) already sits inside such a buffer, that buffer is the answer and nothing is cast.
+    The call also leaves the request on the parameter (``_case_rowpad_multiple``, read by ``rowpad_wanted``): that is how FusedAdam learns,
+    before its first step, which persistent copy to allocate padded.  Without such a copy (f32 compute, another optimizer) the padded copy
+    is rebuilt -- one zero fill and one cast or copy of [Vp, K] -- after every rewrite of the parameter."""
+    if not isinstance(p, torch.nn.Parameter) or p.dim() != 2 or not p.is_contiguous():
+        raise TypeError("cast_param_rowpad: a contiguous 2-D nn.Parameter")
+    p._case_rowpad_multiple = int(multiple)
+    tag = ("rowpad", dtype, int(multiple))
+    hit = paramcache.peek((p,), tag)
+    if hit is not None:
+        return hit
+    low = paramcache.peek((p,), paramcache.cast_tag(p, dtype))
+    buf = getattr(low, "_case_rowpad_buf", None)
+    if buf is not None and buf.shape == (rowpad_rows(p.shape[0], multiple), p.shape[1]) and buf.dtype == dtype and buf.device == p.device:
+        return paramcache.install((p,), tag, buf)
+
+    def build():
+        low = new_rowpad_copy(p, dtype, multiple)
+        if p.dtype == dtype:
+            low.copy_(p.detach())
+        else:
+            A.call("case_cast", _ptr(p), _ptr(low), p.numel(), _code(p), _DT[dtype], _stream())
+        return low._case_rowpad_buf
+    return paramcache.derived((p,), tag, build)
+
+
 def cast(x, dtype):
     if x.dtype == dtype:
         return x
@@ -245,6 +295,12 @@ def _split_for(out_rows, out_cols, k_len, elem_bytes):
     idle (the decoder's 512 x 512 weight gradients: 16 tiles)."""
     k_tiles = max(1, (k_len * elem_bytes + 127) // 128)
     tiles256 = (out_rows // 256) * (out_cols // 256)
+    if elem_bytes == 2 and out_rows % 256 == 0 and out_cols % 256 == 0 and k_len % 64 == 0:
+        # an output whose 256-tiles fill ONE round of the persistent grid by themselves (the row-padded vocabulary gradient: 120 x 2 tiles
+        # over 1280 rows) is not split: a split only adds the zero fill and the atomics
+        cus = max(8, (256 - int(A.lib.case_get_reserved_cus())) // 8 * 8)
+        if 0.9 * cus <= tiles256 <= cus:
+            return 1
     # (one to three 256-tiles cannot fill the chip even at 64 splits -- the reference's default width 256: a 256 x 256 gradient over 16 000
     #  tokens ran as ONE workgroup, 209 us -- so those go to the small tilings below)
     if (elem_bytes == 2 and out_rows % 256 == 0 and out_cols % 256 == 0 and k_len % 64 == 0 and k_tiles >= 64
@@ -2357,6 +2413,122 @@ def pointer_head_score_grad(logits, mix_logits, source_map, rows_per_source, cop
         raise ValueError("pointer_head_score_grad: the memories hold %d positions, the source map %d" % (sum(c.shape[1] for c in copies), keys.shape[1]))
     prob, copy, _ = PointerScoreFn.apply(logits, mix_logits, source_map, rows_per_source, targets.reshape(R).contiguous(), int(pad), *copies)
     return prob, copy
+
+
+# The loss-only head of the TRAINING step: generator rows -> per-row NLL of the mixed pointer-generator distribution without any dense
+# [rows, V] probability tensor.  "auto": wherever the differentiable score head runs (``pointer_score_grad_supported``) and the library
+# exports the loss-form kernels; "dense": the chain masked_softmax, p0 x gen, sorted scatter, add, gather.
+TRAIN_HEAD = os.environ.get("CASE_TRAIN_HEAD", "auto")
+TRAIN_HEAD_PAD = 256  # the vocabulary rows are padded to the edge of the 8-wave GEMM's tile
+
+
+def train_head_supported(source_map, nmem):
+    return (TRAIN_HEAD != "dense" and pointer_score_grad_supported(source_map, nmem)
+            and A.has("case_pointer_head_loss") and A.has("case_pointer_head_loss_bwd"))
+
+
+def pointer_head_loss(logits, V, mix_logits, source_map, rows_per_source, copies, targets, pad=0):
+    """The forward loss kernel as a plain launch: logits f32 [R, ld] (ld >= V; columns [V, ld) are not read), contiguous f32 mix_logits
+    [R, 1 + nmem] and copies [R, len_k], targets int64 [R] -> (prob, copy, stats [R, 2], nll) with K29's prob / copy / stats bits."""
+    R, ld = logits.shape
+    for t in [logits, mix_logits] + list(copies):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("pointer_head_loss: contiguous f32 tensors")
+    if (ld < V or source_map.keys.shape[0] * rows_per_source != R or targets.dtype != torch.int64 or targets.numel() != R
+            or tuple(mix_logits.shape) != (R, len(copies) + 1) or any(c.dim() != 2 or c.shape[0] != R for c in copies)):
+        raise ValueError("pointer_head_loss: shapes do not fit R = %d rows of V = %d (ld %d)" % (R, V, ld))
+    dev = logits.device
+    prob, copy, nll = (torch.empty(R, dtype=torch.float32, device=dev) for _ in range(3))
+    stats = torch.empty(R, 2, dtype=torch.float32, device=dev)
+    lens = C.cast((C.c_int64 * len(copies))(*[c.shape[1] for c in copies]), C.c_void_p)
+    A.call("case_pointer_head_loss", _ptr(logits), ld, _ptr(mix_logits), _ptr(source_map.keys), int(rows_per_source), _copy_pointers(copies), lens,
+           len(copies), _ptr(targets), int(pad), _ptr(prob), _ptr(copy), _ptr(stats), _ptr(nll), R, V, source_map.keys.shape[1], _stream())
+    return prob, copy, stats, nll
+
+
+def pointer_head_loss_bwd(logits, V, mix_logits, ids, rows_per_source, copies, targets, pad, stats, prob, g_nll, dtype=torch.float32, out=None):
+    """The backward loss kernel as a plain launch: the operands of ``pointer_head_loss`` (``ids`` = ``SortedSource.ids``), its stats and prob,
+    g_nll f32 [R] -> (d_logits ``dtype`` [R, ld] with columns [V, ld) zero, d_mix f32 [R, 1 + nmem], [d_copy_k f32 [R, len_k]]), every element
+    written.  ``out``: that triple as buffers to write into."""
+    R, ld = logits.shape
+    d_logits, d_mix, d_cs = out if out is not None else (torch.empty(R, ld, dtype=dtype, device=logits.device), torch.empty_like(mix_logits),
+                                                         [torch.empty_like(c) for c in copies])
+    for t in [logits, mix_logits, stats, prob, g_nll, d_mix] + list(copies) + list(d_cs):
+        if t.dtype != torch.float32 or not t.is_contiguous():
+            raise TypeError("pointer_head_loss_bwd: contiguous f32 tensors")
+    if (ld < V or ld % 8 or ids.dtype != torch.int64 or not ids.is_contiguous() or ids.shape[0] * rows_per_source != R or targets.dtype != torch.int64
+            or targets.numel() != R or tuple(mix_logits.shape) != (R, len(copies) + 1) or tuple(stats.shape) != (R, 2) or prob.numel() != R
+            or g_nll.numel() != R or tuple(d_logits.shape) != (R, ld) or not d_logits.is_contiguous() or d_mix.shape != mix_logits.shape
+            or len(d_cs) != len(copies) or any(c.shape != d.shape or c.dim() != 2 or c.shape[0] != R for c, d in zip(copies, d_cs))):
+        raise ValueError("pointer_head_loss_bwd: shapes do not fit R = %d rows of V = %d (ld %d)" % (R, V, ld))
+    lens = C.cast((C.c_int64 * len(copies))(*[c.shape[1] for c in copies]), C.c_void_p)
+    A.call("case_pointer_head_loss_bwd", _ptr(logits), ld, _ptr(mix_logits), _ptr(ids), int(rows_per_source), _copy_pointers(copies), lens, len(copies),
+           _ptr(targets), int(pad), _ptr(stats), _ptr(prob), _ptr(g_nll), _ptr(d_logits), _code(d_logits), _ptr(d_mix), _copy_pointers(d_cs), R, V,
+           ids.shape[1], _stream())
+    return d_logits, d_mix, d_cs
+
+
+class TrainHeadFn(Function):
+    """h [R, H] (the generator's hidden rows) -> nll f32 [R].  Forward: the vocabulary GEMM into an f32 [R, Vp] buffer against the row-padded
+    operand copy of ``w`` (Vp = V rounded up to 256: the 8-wave tiling takes it; the pad columns come out as exact zeros and are never
+    read), then the forward loss kernel.  Backward: the backward loss kernel writes d_logits [R, Vp] in the operand dtype with zero pad
+    columns, then dX reduces over Vp and dW is computed as [Vp, H] in one unsplit round of tiles -- no zero fill, no atomics -- and
+    returned as its contiguous [:V] prefix.  No host synchronisation."""
+
+    @staticmethod
+    def forward(ctx, h, w, mix_logits, source_map, rows_per_source, targets, pad, *copies):
+        H, V = h.shape[-1], w.shape[0]
+        h2 = h.reshape(-1, H)
+        h2 = h2 if h2.is_contiguous() else h2.contiguous()
+        R = h2.shape[0]
+        wp = cast_param_rowpad(w, h2.dtype, TRAIN_HEAD_PAD)
+        Vp = wp.shape[0]
+        logits = torch.empty(R, Vp, dtype=torch.float32, device=h2.device)
+        gemm(h2, wp, logits, R, Vp, H, H, H, Vp)
+        mix32 = mix_logits.reshape(R, -1).float().contiguous()
+        cs = [c.reshape(R, -1).float().contiguous() for c in copies]
+        targets = targets.reshape(R).contiguous()
+        prob, _, stats, nll = pointer_head_loss(logits, V, mix32, source_map, rows_per_source, cs, targets, pad)
+        ctx.save_for_backward(h2, wp, logits, mix32, targets, stats, prob, source_map.ids, *cs)
+        ctx.meta = (h.shape, V, rows_per_source, pad, mix_logits.shape, mix_logits.dtype, [(c.shape, c.dtype) for c in copies])
+        return nll
+
+    @staticmethod
+    def backward(ctx, g_nll):
+        h2, wp, logits, mix32, targets, stats, prob, ids = ctx.saved_tensors[:8]
+        cs = list(ctx.saved_tensors[8:])
+        hshape, V, rows_per_source, pad, mix_shape, mix_dtype, copy_meta = ctx.meta
+        (R, H), Vp = h2.shape, wp.shape[0]
+        d_logits, d_mix, d_cs = pointer_head_loss_bwd(logits, V, mix32, ids, rows_per_source, cs, targets, pad, stats, prob,
+                                                      g_nll.reshape(R).float().contiguous(), dtype=h2.dtype)
+        dh = _input_grad(d_logits, wp, R, H, Vp).view(hshape) if ctx.needs_input_grad[0] else None
+        dw = None
+        if ctx.needs_input_grad[1]:
+            if _split_for(Vp, H, R, h2.element_size()) == 1:
+                dwp = torch.empty(Vp, H, dtype=torch.float32, device=h2.device)
+                gemm(d_logits, h2, dwp, Vp, H, R, Vp, H, H, a_kmajor=True, b_kmajor=True)
+            else:
+                dwp = _weight_grad(d_logits, h2, Vp, H)
+            dw = dwp[:V]
+        return (dh, dw, d_mix.view(mix_shape).to(mix_dtype), None, None, None, None) + tuple(d.view(sh).to(dt) for d, (sh, dt) in zip(d_cs, copy_meta))
+
+
+def train_head_nll(h, w, mix_logits, source_map, rows_per_source, copies, targets, pad=0):
+    """The loss-only training head (``TrainHeadFn``): h [R, H] of the compute dtype, w the [V, H] vocabulary projection (an nn.Parameter),
+    mix_logits [R, 1 + nmem], source_map a SortedSource with R / rows_per_source rows, copies [R, len_k], targets int64 [R] -> nll f32 [R]
+    = -log(p(target) + 1e-8), 0 where target == pad; differentiable in h, w, mix_logits and every copies[k]."""
+    if not isinstance(source_map, SortedSource) or not 1 <= len(copies) <= 4:
+        raise TypeError("train_head_nll: a SortedSource and 1 .. 4 memories")
+    if not (A.has("case_pointer_head_loss") and A.has("case_pointer_head_loss_bwd")):
+        raise RuntimeError("train_head_nll: this build of the library lacks case_pointer_head_loss / case_pointer_head_loss_bwd")
+    R = h.numel() // h.shape[-1]
+    rows_per_source = int(rows_per_source)
+    if rows_per_source < 1 or source_map.keys.shape[0] * rows_per_source != R or targets.numel() != R or targets.dtype != torch.int64:
+        raise ValueError("train_head_nll: %d rows, %d key rows, rows_per_source %d, %d targets" % (R, source_map.keys.shape[0], rows_per_source,
+                                                                                               targets.numel()))
+    if sum(c.shape[-1] for c in copies) != source_map.keys.shape[1]:
+        raise ValueError("train_head_nll: the memories hold %d positions, the source map %d" % (sum(c.shape[-1] for c in copies), source_map.keys.shape[1]))
+    return TrainHeadFn.apply(h, w, mix_logits, source_map, rows_per_source, targets, int(pad), *copies)
 
 
 # K42: the expected cost of a pool of candidates under the renormalised model posterior (evaluation/risk.py states the rule).

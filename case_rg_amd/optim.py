@@ -161,8 +161,10 @@ class FusedAdam(torch.optim.Optimizer):
                 lp = None
                 if self.low_precision is not None and p.dim() > 1:
                     lp = self._low.get(id(p))
-                    if lp is None or lp.shape != p.shape or lp.device != dev:
-                        lp = self._low[id(p)] = torch.empty(p.shape, dtype=self.low_precision, device=dev)
+                    pad = ops.rowpad_wanted(p) if p.dim() == 2 else 0  # (a GEMM reads the copy with its rows padded: ops.cast_param_rowpad)
+                    if lp is None or lp.shape != p.shape or lp.device != dev or (pad and getattr(lp, "_case_rowpad_buf", None) is None):
+                        lp = self._low[id(p)] = (ops.new_rowpad_copy(p, self.low_precision, pad) if pad
+                                                 else torch.empty(p.shape, dtype=self.low_precision, device=dev))
                     fresh.append((p, lp))
                 rows.append((_Entry(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr(),
                                            0 if sh is None else sh.data_ptr(), 0 if lp is None else lp.data_ptr(), p.numel(),

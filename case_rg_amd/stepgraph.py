@@ -107,6 +107,9 @@ class StepGraphs(object):
                 for p in optimizer.last_stepped:  # host-side effects of a recording pass that executed nothing
                     optimizer.state[p]["step"] = int(optimizer.state[p]["step"]) - 1
                 config.skip_rng(before - config.rng_state()[1])
+                # a parameter copy the recording pass derived (ops.cast_param_rowpad: the padded vocabulary operand) was registered but never
+                # computed: forget everything but the optimizer's persistent copies, which prepare_capture refreshed eagerly
+                paramcache.rewritten(keep=optimizer.low_copies())
                 optimizer.zero_grad()
                 if tr.sync is not None:
                     tr.sync.no_sync(False)

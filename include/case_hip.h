@@ -989,6 +989,28 @@ int case_pointer_head_score_bwd(const float* logits, const float* mix_logits, co
 int case_sequence_risk(const float* token_probs, const uint8_t* scored, const float* cost, const uint8_t* valid, double alpha, float* risk,
                        float* q, float* grad_p, int64_t B, int64_t N, int64_t T, case_stream_t stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * The loss-only head of the training step (purely additive, generation 600 unchanged).  The 32-bit feature mask is full: a caller
+ * detects the pair by symbol lookup (dlsym of case_pointer_head_loss).
+ * case_pointer_head_loss: case_pointer_head_score_stats over logits rows `ld_logits` floats apart (ld_logits >= V, a multiple of 4, on a
+ *   16-byte base: the rows of a vocabulary GEMM whose N is padded to its tile; columns [V, ld_logits) are never read), with one more
+ *   output: nll f32 [R] = -log(prob + 1e-8), 0 for a row whose target is `pad`.  prob / copy / stats carry the bits
+ *   case_pointer_head_score_stats gives for the same logits values in a contiguous [R, V] buffer on a 16-byte boundary.  stats and nll
+ *   are required.
+ * case_pointer_head_loss_bwd: K41 for that loss.  g_nll f32 [R] = dL/dnll; the kernel uses g = -g_nll / (prob + 1e-8) where K41 takes
+ *   dL/dprob.  logits and d_logits rows lie `ld_logits` elements apart (>= V, a multiple of 8, 16-byte bases).  d_logits has `d_dtype`
+ *   (CASE_F32 or CASE_BF16: K41's f32 expression rounded once to nearest even) and EVERY element of it is written: columns
+ *   [V, ld_logits) as zeros, so a GEMM may reduce over the padded width.  d_mix and d_copies as K41.
+ * Limits, determinism and error codes as K29 / K41.  Both are asynchronous on `stream`.
+ * ------------------------------------------------------------------------------------------- */
+int case_pointer_head_loss(const float* logits, int64_t ld_logits, const float* mix_logits, const uint32_t* keys, int64_t rows_per_source,
+                           const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad, float* prob,
+                           float* copy, float* stats, float* nll, int64_t R, int64_t V, int64_t S, case_stream_t stream);
+int case_pointer_head_loss_bwd(const float* logits, int64_t ld_logits, const float* mix_logits, const int64_t* ids, int64_t rows_per_source,
+                               const float* const* copies, const int64_t* lens, int32_t nmem, const int64_t* targets, int64_t pad,
+                               const float* stats, const float* prob, const float* g_nll, void* d_logits, int32_t d_dtype, float* d_mix,
+                               float* const* d_copies, int64_t R, int64_t V, int64_t S, case_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
