@@ -13,7 +13,10 @@ attention  the first C <= min(d, 8) head dimensions carry a class code: key j of
            [-127, 127]; O is the exact class mean.
 K8         the same class code carried over to the co-attention's rank-1 score (see "K8" below): every entry of A and Bm^T is 1/n or 0,
            and the kernels' bf16 roundings are restated at the points where they round (interaction_restated).
-K16        the encoder chain's parameters written so that each stage stands alone (see "K16" below): integers, signed permutations, zeros."""
+K16        the encoder chain's parameters written so that each stage stands alone (see "K16" below): integers, signed permutations, zeros.
+K7 / K22   the additive attention (see "K7 / K22" below): a ternary family whose tanh is 0 or +-1, a mid-range family with the float64
+           restatement AND its derived error bound per arithmetic form, the launch rules restated (k7_paths); pinned by
+           tests/test_additive_exact_cpu.py."""
 import torch
 
 F64 = torch.float64
@@ -680,3 +683,347 @@ def chain_ffn(lay, rows=1):
     pre = lay["W1"] @ s2 + lay["b1"]
     a = torch.where(pre > 0, pre, torch.zeros_like(pre))
     return s2, a, lay["W2"] @ a + lay["b2"] + s2
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# K7 / K22: the additive attention  s[b,t,j] = sum_h v_h tanh(wq[b,t,h] + uh[b,j,h])  (csrc/attn_pointer.hip)
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Two operand families.
+#   ternary    wq = 10 sw, uh = 10 su with seeded random signs: wq + uh is 0 or +-20, tanh is 0 or +-1 and 1 - tanh^2 is 1 or 0 (to below
+#              1e-16); v in {+-1, +-2}, ds integers in [-3, 3].  s, d_wq, d_uh and d_v are integers below 2^24 that depend on every one of
+#              b, t, j, h, so the f32 path (tanhf is exact at 0 and at +-20) must give the float64 restatement in every bit, through any
+#              summation order and any split with atomics.  10 is exact in bf16 and inside the +-21.4 clamp of the factored form.
+#   mid-range  normal operands at scale 1.5 (v at 0.3, ds at 1): the numerics -- the prescale, the factors 4 and 2, the clamp.
+# k7_reference is the float64 restatement TOGETHER with its error bound, element by element, per arithmetic form of the kernels.  With
+# u = 2^-24 and first-order terms only (every constant carries a factor 1 + 2^-10 for the higher orders):
+#   "tanhf"     th = tanhf(fl(w + u)): the rounded sum moves tanh by u |x| (1 - th^2), tanhf itself by EPS_TANHF |th|.
+#               1 - th th: two more roundings, |d(1 - th^2)| <= 2 |th| dth + 2 u.
+#   "factored"  ws = fl(PS w), us = fl(PS u), PS = fl(2 / ln 2): each prescaled argument is off by ARG = 2 u relative (the constant's rounding
+#               and the product's), which moves 2^ws 2^us by the factor (|ws| + |us|) ln 2 ARG = 2 (|w| + |u|) ARG; the two v_exp_f32 add
+#               EPS_EXP each:  eta = 2 (|w| + |u|) ARG + 2 EPS_EXP  is the relative error of E = e^{2x} as the kernel has it.
+#               r = rcp(fma(ew, eu, 1)): d r / d ln E = -r (1 - r); the fma's rounding and v_rcp_f32 are relative errors of r itself:
+#               dr = r (1 - r) eta + r (u + EPS_RCP);  tanh = 1 - 2 r: dth = 2 dr;  1 - tanh^2 = 4 r (1 - r), taken as g r - (g r) r:
+#               |d(4 r (1 - r))| <= 4 |1 - 2 r| dr + 8 u r  (three roundings of magnitude <= g r).
+#   "exp2x"     the row-wise bf16 kernel: 1 - __fdividef(2, __expf(2 fl(w + u)) + 1).  __expf(y) is v_exp_f32(fl(y log2 e)): relative error
+#               |y| ARG + EPS_EXP, and the rounded sum adds 2 u |x|: eta = 6 u |x| + EPS_EXP;  dr = r (1 - r) eta + r (u + EPS_FDIV),
+#               dth = 2 dr + u |th| (the final subtraction).
+#   "cached"    K22: E = EW eu with eu the kernel's own bf16 input (exact) and EW = __expf(clip(2 w)): eta = |2 w| ARG + EPS_EXP, dr as in
+#               "factored" (k22_reference).
+# Sums: n terms accumulated in f32 in ANY order (sequential, tree, partial sums added with atomics) err by at most (n + c) u sum |term|; c
+# counts the roundings outside the sum (each term's product, the factor v_h or 4 v_h, the final subtraction).  The forward of the factored
+# form is vsum - 2 acc with acc = sum v r: 2 (H + 2) u sum |v| (r <= 1 and the v-sum share one bar); its d_v is gsum - 2 dv in the same way.
+U32 = 2.0 ** -24 * (1 + 2.0 ** -10)
+ULP32 = 2 * U32            # one ulp as a relative error: 2^-23 2^e <= 2^-23 |y|
+EPS_EXP = 1 * ULP32        # v_exp_f32: 1 ulp (CDNA4 ISA guide, VOP1 transcendental accuracy)
+EPS_RCP = 1 * ULP32        # v_rcp_f32: 1 ulp (same table)
+EPS_FDIV = 2 * ULP32       # __fdividef: 2 ulp (HIP math API, single-precision intrinsics; the table is not in the ROCm tree, CUDA's lists the same)
+EPS_TANHF = 5 * ULP32      # tanhf: OpenCL 3.0 table 7.4 (tanh <= 5 ulp); the HIP math API table is not in the ROCm tree
+ARG32 = 2 * U32
+K7_A = 10.0
+K7_CLAMP = 21.0            # inputs stay inside |x| <= 21: the factored form's clamp (+-62 / (2 / ln 2) = 21.49) never acts
+K7_FORMS = ("tanhf", "factored", "exp2x")
+
+
+def k7_ternary(B, T, S, H, seed):
+    """(wq [B,T,H], uh [B,S,H], v [H], ds [B,T,S]) in float64, all exact in bf16."""
+    g = _gen(seed)
+    pm = lambda *shape: (torch.randint(0, 2, shape, generator=g) * 2 - 1).to(F64)
+    wq, uh = K7_A * pm(B, T, H), K7_A * pm(B, S, H)
+    v = pm(H) * torch.randint(1, 3, (H,), generator=g).to(F64)
+    ds = torch.randint(-3, 4, (B, T, S), generator=g).to(F64)
+    return wq, uh, v, ds
+
+
+def k7_midrange(B, T, S, H, seed):
+    """The same four operands, normal: wq, uh at scale 1.5 (cut at +-K7_CLAMP / 2, so that |wq + uh| <= 21), v at 0.3, ds at 1; rounded to f32
+    (the caller rounds uh once more where the kernel reads bf16)."""
+    g = _gen(seed)
+    rn = lambda scale, *shape: (torch.randn(shape, generator=g) * scale).to(torch.float32).to(F64)
+    half = K7_CLAMP / 2
+    return rn(1.5, B, T, H).clamp(-half, half), rn(1.5, B, S, H).clamp(-half, half), rn(0.3, H), rn(1.0, B, T, S)
+
+
+K7_FAMILIES = {"ternary": k7_ternary, "mid": k7_midrange}
+
+
+def k7_seed(B, T, S, H):
+    return (B * 1000003 + T * 10007 + S * 101 + H) % (2 ** 31)
+
+
+def k7_element(form, w, u, prescale=1.0):
+    """(tanh, 1 - tanh^2, bound on the kernel's tanh, bound on the kernel's 1 - tanh^2) of w + u, broadcast, float64."""
+    x = (w + u) * prescale
+    th = torch.tanh(x)
+    r = torch.sigmoid(-2.0 * x)          # 1 / (e^{2x} + 1)
+    gp = 4.0 * r * (1.0 - r)             # 1 - tanh^2 without the cancellation
+    if form == "tanhf":
+        dth = U32 * x.abs() * gp + EPS_TANHF * th.abs()
+        return th, gp, dth, 2.0 * th.abs() * dth + 2.0 * U32
+    if form == "factored":
+        eta = 2.0 * (w.abs() + u.abs()) * ARG32 + 2.0 * EPS_EXP
+        dr = r * (1.0 - r) * eta + r * (U32 + EPS_RCP)
+        return th, gp, 2.0 * dr, 4.0 * (1.0 - 2.0 * r).abs() * dr + 8.0 * U32 * r
+    if form == "exp2x":
+        eta = 6.0 * U32 * x.abs() + EPS_EXP
+        dr = r * (1.0 - r) * eta + r * (U32 + EPS_FDIV)
+        return th, gp, 2.0 * dr + U32 * th.abs(), None
+    raise ValueError(form)
+
+
+def k7_reference(wq, uh, v, ds=None, form="tanhf", prescale=1.0, limit=1 << 22):
+    """float64 restatement on the device of the operands, in chunks over the items so that no [b, T, S, H] temporary exceeds ``limit``
+    elements (32 MB).  -> {name: (value, bound)} for s and, with ``ds``, d_wq, d_uh, d_v."""
+    B, T, H = wq.shape
+    S = uh.shape[1]
+    assert T * S * H <= 1 << 23, "one item alone is too large for a chunk"
+    nb = max(1, limit // (T * S * H))
+    c = 2 if form == "factored" else 1
+    av, z = v.abs(), lambda *shape: torch.zeros(shape, dtype=F64, device=wq.device)
+    s, s_b = z(B, T, S), z(B, T, S)
+    if ds is not None:
+        d_wq, d_wq_b, d_uh, d_uh_b, d_v, d_v_b, d_v_abs = z(B, T, H), z(B, T, H), z(B, S, H), z(B, S, H), z(H), z(H), z(H)
+    for b0 in range(0, B, nb):
+        sl = slice(b0, min(B, b0 + nb))
+        th, gp, dth, dgp = k7_element(form, wq[sl, :, None, :], uh[sl, None, :, :], prescale)
+        s[sl] = (th * v).sum(-1)
+        s_b[sl] = (dth * av).sum(-1) + c * (H + 2) * U32 * av.sum()
+        if ds is None:
+            continue
+        g = ds[sl, :, :, None]
+        ag = g.abs()
+        d_uh[sl] = v * (g * gp).sum(1)
+        d_uh_b[sl] = av * ((ag * dgp).sum(1) + (T + 4) * U32 * (ag * gp).sum(1))
+        d_wq[sl] = v * (g * gp).sum(2)
+        d_wq_b[sl] = av * ((ag * dgp).sum(2) + (S + 4) * U32 * (ag * gp).sum(2))
+        d_v += (g * th).sum((0, 1, 2))
+        d_v_b += (ag * dth).sum((0, 1, 2))
+        d_v_abs += (ag * th.abs()).sum((0, 1, 2)) if c == 1 else ag.sum()
+    out = {"s": (s, s_b)}
+    if ds is not None:
+        out.update(d_wq=(d_wq, d_wq_b), d_uh=(d_uh, d_uh_b), d_v=(d_v, d_v_b + c * (B * T * S + 4) * U32 * d_v_abs))
+    return out
+
+
+def k7_ternary_exact(ref):
+    """The ternary family's float64 result is an integer or a half-integer up to the 1e-16 that 1 - tanh(20)^2 leaves: that number itself."""
+    exact = torch.round(2.0 * ref) / 2.0
+    assert float((ref - exact).abs().max()) < 1e-9 and float(exact.abs().max()) < 2 ** 24
+    return exact
+
+
+def k7_emulate(form, wq, uh, v, ds=None):
+    """The kernels' arithmetic in float32 on the host (torch's exp2 / exp / tanh and a true division where the device has v_exp_f32,
+    v_rcp_f32 and tanhf; torch's own summation order) -> {name: f32 tensor}: what a correct kernel may return, up to the instructions' own error."""
+    f = lambda t: t.to(torch.float32)
+    wq, uh, v = f(wq), f(uh), f(v)
+    one = torch.tensor(1.0, dtype=torch.float32)
+    if form == "factored":
+        ps = torch.tensor(2.8853900817779268, dtype=torch.float32)
+        ew, eu = torch.exp2((ps * wq).clamp(-62.0, 62.0)), torch.exp2((ps * uh).clamp(-62.0, 62.0))
+        r = one / (ew[:, :, None, :] * eu[:, None, :, :] + one)
+        out = {"s": v.sum() - 2.0 * (v * r).sum(-1)}
+        if ds is not None:
+            g = f(ds)[..., None]
+            gr = g * r
+            q = gr - gr * r
+            out.update(d_uh=4.0 * v * q.sum(1), d_wq=4.0 * v * q.sum(2), d_v=g.expand_as(gr).sum((0, 1, 2)) - 2.0 * gr.sum((0, 1, 2)))
+        return out
+    x = wq[:, :, None, :] + uh[:, None, :, :]
+    th = torch.tanh(x) if form == "tanhf" else one - 2.0 / (torch.exp(2.0 * x) + one)
+    out = {"s": (v * th).sum(-1)}
+    if ds is not None:
+        g = f(ds)[..., None]
+        q = g * (one - th * th)
+        out.update(d_uh=v * q.sum(1), d_wq=v * q.sum(2), d_v=(g * th).sum((0, 1, 2)))
+    return out
+
+
+def k7_form(path, dtype):
+    """The arithmetic form the launcher's choice computes with: f32 -> tanhf everywhere; bf16 -> factored (tiled forward, both backward
+    sweeps) or exp(2x) with a division (row-wise forward)."""
+    if dtype == torch.float32:
+        return "tanhf"
+    return "exp2x" if path == "rowwise" else "factored"
+
+
+def k7_paths(B, T, S, H, dtype, aligned=True):
+    """The launch rules of case_additive_scores_fwd / _bwd restated: (set of path names, dict of the launchers' figures)."""
+    cdiv = lambda a, b: (a + b - 1) // b
+    ev = 4 if dtype == torch.float32 else 8
+    p, fig = set(), {}
+    if T <= 2 and H % ev == 0 and H <= 2 * 64 * ev and aligned:
+        nch = 1 if H <= 64 * ev else 2
+        wgs = min(cdiv(S, 16), 64)
+        p |= {"fwd.rowwise", "fwd.rowwise.T%d" % T, "fwd.rowwise.NCH%d" % nch, "fwd.rowwise.T%d.NCH%d" % (T, nch)}
+        if S > 4 * wgs:
+            p.add("fwd.rowwise.stride")
+        if cdiv(S, 16) > 64 and S > 1024:
+            p.add("fwd.rowwise.capped")
+        fig.update(fwd="rowwise", nch=nch, wgs=wgs)
+    else:
+        jb, tchunks = cdiv(S, 64), cdiv(T, 32)
+        p.add("fwd.tiled")
+        if T <= 2:
+            p.add("fwd.fallback.h_mod" if H % ev else "fwd.fallback.h_wide" if H > 2 * 64 * ev else "fwd.fallback.misaligned")
+        if tchunks > 1:
+            p.add("fwd.tiled.zstride" if jb * B < 512 else "fwd.tiled.loop")
+        if H > 64:
+            p.add("fwd.tiled.hchunks")
+        for name, n, tile in (("h", H, 64), ("j", S, 64), ("t", T, 32)):
+            if n % tile:
+                p.add("fwd.tiled.ragged_" + name)
+        fig.update(fwd="tiled", jb=jb, tchunks=tchunks, gz=tchunks if jb * B < 512 else 1)
+    hb, tblocks, j_chunks = cdiv(H, 256), cdiv(T, 8), cdiv(S, 64)
+    base = tblocks * hb * B
+    sch = min(1 if base >= 2048 else cdiv(2048, base), j_chunks)
+    j_per = cdiv(j_chunks, sch) * 64
+    sch = cdiv(S, j_per)
+    if hb > 1:
+        p.add("bwd.hblocks")
+    if sch > 1:
+        p.add("bwd.wq.split")
+        if j_per > 64:
+            p.add("bwd.wq.split.multichunk")
+        if S % j_per:
+            p.add("bwd.wq.split.ragged")
+    else:
+        p.add("bwd.wq.unsplit")
+        p.add("bwd.wq.unsplit.multichunk" if j_chunks > 1 else "bwd.wq.unsplit.onechunk")
+    if T > 32:
+        p.add("bwd.uh.tstage")
+    if S < 16:
+        p.add("bwd.uh.s_lt16")
+    if S % 16:
+        p.add("bwd.uh.ragged_s")
+    fig.update(hb=hb, tblocks=tblocks, base_wgs=base, sch=sch, j_per=j_per, last_range=S - (sch - 1) * j_per)
+    return p, fig
+
+
+# (B, T, S, H): the smallest shapes that reach each path (tests/test_additive_exact_cpu.py asserts the reach)
+K7_FWD_TILED = [(2, 3, 1, 1), (2, 32, 63, 63), (2, 33, 64, 64), (1, 3, 65, 65), (2, 11, 150, 96), (2, 70, 150, 512), (512, 70, 33, 8)]
+K7_FWD_ROWWISE = {  # (B, T, S, H, aligned)
+    torch.float32: [(2, 1, 77, 4, True), (2, 2, 1, 256, True), (1, 1, 1030, 260, True), (2, 2, 77, 512, True),
+                    (2, 1, 77, 6, True), (2, 2, 77, 516, True), (2, 1, 77, 256, False)],
+    torch.bfloat16: [(2, 1, 77, 8, True), (2, 2, 1, 512, True), (1, 1, 1030, 520, True), (2, 2, 77, 1024, True),
+                     (2, 1, 77, 1032, True), (2, 2, 77, 512, False)],
+}
+K7_BWD = [(2, 1, 1, 1), (2, 7, 15, 255), (1, 8, 16, 256), (2, 9, 17, 257), (2, 33, 64, 512), (1, 65, 65, 8),
+          (2, 40, 200, 512), (128, 64, 300, 8), (256, 64, 130, 8)]
+K7_FWD_PATHS = {"fwd.tiled.zstride", "fwd.tiled.loop", "fwd.tiled.hchunks", "fwd.tiled.ragged_h", "fwd.tiled.ragged_j", "fwd.tiled.ragged_t",
+                "fwd.rowwise.T1.NCH1", "fwd.rowwise.T1.NCH2", "fwd.rowwise.T2.NCH1", "fwd.rowwise.T2.NCH2", "fwd.rowwise.stride",
+                "fwd.rowwise.capped", "fwd.fallback.h_mod", "fwd.fallback.h_wide", "fwd.fallback.misaligned"}
+K7_BWD_PATHS = {"bwd.hblocks", "bwd.wq.split", "bwd.wq.split.multichunk", "bwd.wq.split.ragged", "bwd.wq.unsplit.multichunk",
+                "bwd.wq.unsplit.onechunk", "bwd.uh.tstage", "bwd.uh.s_lt16", "bwd.uh.ragged_s"}
+
+
+# K22 ---------------------------------------------------------------------------------------------------------------------------------
+K22_H, K22_CLAMP, K22_MAX_S = 512, 43.0, 28000
+TINY32 = 2.0 ** -120       # an f32 exponential that underflows is flushed: absolute, far below every probability compared here
+
+
+def key_exp_reference(x):
+    """case_additive_key_exp in float64 -> (e^{clip(2x, +-43)}, the f32 error of __expf in front of the one rounding to bf16)."""
+    y = (2.0 * x.to(F64)).clamp(-K22_CLAMP, K22_CLAMP)
+    ref = torch.exp(y)
+    return ref, ref * (y.abs() * ARG32 + EPS_EXP)
+
+
+def k22_depths(S, H=K22_H):
+    """The most additions one term passes through in K22's three sums: (score: H / 64 per lane + 6 tree levels over the lanes; softmax sum and
+    prior sum: ceil(S / 1024) per thread + 6 levels over the lanes + 6 over the 16 waves' partial sums; context: ceil(S / 16) rows per wave
+    + 16 partial sums)."""
+    return H // 64 + 6, -(-S // 1024) + 12, -(-S // 16) + 16
+
+
+def k22_reference(w, eu, v, mem, cv=None, rv=None, prior=None, limit=1 << 22):
+    """K22 in float64 from the kernel's own inputs: w [B, H] (the f32 sum wq + wq_add, upcast), eu / mem [B, S, H] (the bf16 tensors, upcast),
+    v [H], masks bool, prior [B, S] -> {name: (value, bound)} for s, p, copy (with a prior) and ctx (the bound is the f32 one: the caller adds
+    the one rounding to bf16).
+    Sums: a term that passes through at most D additions errs by D u sum |term| whatever the order; the depths are the kernel's (a rewrite
+    that sums no deeper meets them too): k22_depths.
+      s     = sum v - 2 sum_h v_h r_h, r = rcp(fma(EW, eu, 1)): form "cached" above; each lane sums its 8 features, a reduction tree over the
+              64 lanes follows (D = 14), for sum v and for sum v r alike, + 2 for the product and the last subtraction:
+              2 sum |v_h| dr_h + 3 (D + 2) u sum |v|.
+      p_j   = e_j / sum e, e_j = __expf(s_j - m) for ANY m (the softmax does not depend on the shift, so the kernel's maximum need not be the
+              reference's): relative error rho_j = ds_j + u |y_j| (the subtraction) + |y_j| ARG + EPS_EXP (__expf); the sum of S positive
+              terms (S / 1024 per thread, then trees over lanes and waves) has the p-weighted mean of the rho plus D_S u; 1 / sum, and the
+              product: two more.  rel_j = rho_j + sum p rho + (D_S + 4) u.
+      copy  = p prior / (1e-8f + sum p prior): rel_j + the (p prior)-weighted mean of the rel + (D_S + 6) u.
+      ctx_h = sum_j p_j mem_jh: each of the 16 waves takes every 16th row by FMAs, the 16 partial sums are added in sequence (D_C):
+              sum |dp_j| |mem_jh| + (D_C + 2) u sum p_j |mem_jh|.
+    Masked positions, an item without a valid position and an invalid target row give exact zeros (bound 0)."""
+    B, S, H = eu.shape
+    dev = eu.device
+    nb = max(1, limit // (S * H))
+    av = v.abs()
+    d_s, d_sum, d_ctx = k22_depths(S, H)
+    s, s_b = torch.empty(B, S, dtype=F64, device=dev), torch.empty(B, S, dtype=F64, device=dev)
+    for b0 in range(0, B, nb):
+        sl = slice(b0, min(B, b0 + nb))
+        y = (2.0 * w[sl, None, :]).clamp(-K22_CLAMP, K22_CLAMP)
+        r = 1.0 / (torch.exp(y) * eu[sl] + 1.0)
+        dr = r * (1.0 - r) * (y.abs() * ARG32 + EPS_EXP) + r * (U32 + EPS_RCP)
+        s[sl] = v.sum() - 2.0 * (v * r).sum(-1)
+        s_b[sl] = 2.0 * (av * dr).sum(-1) + 3.0 * (d_s + 2) * U32 * av.sum()
+    valid = torch.ones(B, S, dtype=torch.bool, device=dev) if cv is None else cv.clone()
+    live = valid.any(-1) if rv is None else valid.any(-1) & rv
+    sm = s.masked_fill(~valid, float("-inf"))
+    m = torch.where(valid.any(-1), sm.max(-1).values, torch.zeros(B, dtype=F64, device=dev))
+    yj = torch.where(valid, s - m[:, None], torch.zeros_like(s))
+    e = torch.where(valid, torch.exp(yj), torch.zeros_like(s))
+    p = torch.where(live[:, None], e / e.sum(-1, keepdim=True).clamp_min(1e-300), torch.zeros_like(e))
+    rho = torch.where(valid, s_b + yj.abs() * (U32 + ARG32) + EPS_EXP, torch.zeros_like(s))
+    rel = rho + (p * rho).sum(-1, keepdim=True) + (d_sum + 4) * U32
+    p_b = torch.where(p > 0, p * torch.expm1(rel) + TINY32, torch.zeros_like(p))
+    out = {"s": (s, s_b), "p": (p, p_b)}
+    if prior is not None:
+        pw = p * prior
+        den = float(torch.tensor(1e-8, dtype=torch.float32)) + pw.sum(-1, keepdim=True)
+        crel = rel + (pw * rel).sum(-1, keepdim=True) / den + (d_sum + 6) * U32
+        out["copy"] = (pw / den, torch.where(pw > 0, pw / den * torch.expm1(crel) + TINY32, torch.zeros_like(pw)))
+    ctx, ctx_b = torch.empty(B, H, dtype=F64, device=dev), torch.empty(B, H, dtype=F64, device=dev)
+    for b0 in range(0, B, nb):
+        sl = slice(b0, min(B, b0 + nb))
+        ctx[sl] = torch.einsum("bs,bsh->bh", p[sl], mem[sl])
+        am = mem[sl].abs()
+        ctx_b[sl] = torch.einsum("bs,bsh->bh", p_b[sl], am) + (d_ctx + 2) * U32 * torch.einsum("bs,bsh->bh", p[sl], am)
+    out["ctx"] = (ctx, ctx_b)
+    return out
+
+
+def k22_emulate(w, eu, v):
+    """K22's scores in float32 on the host (torch's exp and a true division for __expf and v_rcp_f32)."""
+    w, eu, v = w.to(torch.float32), eu.to(torch.float32), v.to(torch.float32)
+    ew = torch.exp((2.0 * w).clamp(-K22_CLAMP, K22_CLAMP))
+    return v.sum() - 2.0 * (v / (ew[:, None, :] * eu + 1.0)).sum(-1)
+
+
+def k22_midrange(B, S, seed, H=K22_H):
+    """(wq [B,H], uh [B,S,H], v [H], mem [B,S,H]) float64: wq, uh normal at 1.5 and rounded to f32, v at 0.3, mem normal rounded to bf16."""
+    g = _gen(seed)
+    rn = lambda scale, *shape: (torch.randn(shape, generator=g) * scale).to(torch.float32).to(F64)
+    return rn(1.5, B, H), rn(1.5, B, S, H), rn(0.3, H), rn(1.0, B, S, H).to(torch.bfloat16).to(F64)
+
+
+def k22_ternary(B, S, n, seed, H=K22_H):
+    """An exact K22 case: wq = 10 sw with random signs, v in {+-1, +-2}.  ``n`` rows of every item (a power of two, scattered by a seeded
+    permutation) form the best class: uh = 10 sign(v) where sw = sign(v) (tanh(20) = sign(v): the term is |v|), -wq elsewhere (tanh(0) = 0).
+    Every other row is the worst: uh = -10 sign(v) where sw = -sign(v) (the term is -|v|), -wq elsewhere.  The class's score is
+    sum_{sw = sign v} |v| (about 384), the others' -sum_{sw = -sign v} |v|: apart by sum |v| >= 512, and e^-512 is 0 in f32 and in float64.
+    The rows of a class are the same bits, so their scores are; p is exactly 1 / n on the class and exactly 0 elsewhere, and with integer
+    memory rows ctx is the exact class mean (one rounding to bf16).  eu = bf16(e^{+-20}) carries a rounding: the class scores move by
+    2^-9 sum |v|, all alike.  -> (wq, uh, v, mem, best [B, S] bool), float64."""
+    assert n & (n - 1) == 0 and n <= S
+    g = _gen(seed)
+    pm = lambda *shape: (torch.randint(0, 2, shape, generator=g) * 2 - 1).to(F64)
+    sw, sv = pm(B, H), pm(H)
+    v = sv * torch.randint(1, 3, (H,), generator=g).to(F64)
+    agree = sw == sv
+    top = torch.where(agree, sv.expand(B, H), -sw)      # [B, H]
+    low = torch.where(~agree, -sv.expand(B, H), -sw)
+    best = torch.zeros(B, S, dtype=torch.bool)
+    for b in range(B):
+        best[b, torch.randperm(S, generator=g)[:n]] = True
+    uh = K7_A * torch.where(best[:, :, None], top[:, None, :], low[:, None, :])
+    mem = torch.randint(-V_BOUND, V_BOUND + 1, (B, S, H), generator=g).to(F64)
+    return K7_A * sw, uh, v, mem, best
