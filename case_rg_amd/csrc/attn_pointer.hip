@@ -6,6 +6,8 @@
 //   backward  two sweeps with lanes = h (coalesced uh reads, no cross-lane reductions, no atomics on the
 //             large tensors): sweep 1 owns (j, h) and sums over t -> d_uh and the d_v partials;
 //             sweep 2 owns (t, h) and sums over j -> d_wq.  tanh is recomputed in both.
+#include <type_traits>
+
 #include "common.h"
 
 namespace {
@@ -1742,43 +1744,10 @@ constexpr int64_t PH_MAX_V = 36000, PS_MAX_V = 131071;  // the vocabulary row in
 // 2^(40 - e)), so V <= 2^24 keeps every 64-bit sum below 2^64; the entry counts and the int ids need less
 constexpr int64_t PW_MAX_DIST_V = 1ll << 24;
 
-static int pointer_head_args(HeadArgs& a, const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
-                             const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t B, int64_t V, int64_t S,
-                             bool wide = false) {
-  const int rc = pointer_head_fill(a, who, logits, mix_logits, keys, copies, lens, nmem, B, V, S, wide ? PS_MAX_V : PH_MAX_V,
-                                   wide ? "" : " (run the softmax / scatter / argmax launches)");
-  if (rc != CASE_OK) return rc;
-  a.gen = gen;
-  a.dist = dist;
-  a.ids = nullptr;
-  a.top = nullptr;
-  a.row_ws = nullptr;
-  a.row_stride = 0;
-  return CASE_OK;
-}
-
 // the LDS forms: the row, the key staging and the reduction scratch; the wide forms (V = 0): the staging and the scratch alone
 static size_t pointer_head_lds(int64_t V) { return (size_t)(((V + 3) & ~(int64_t)3) + (PH_THREADS + 4) + PH_THREADS + 64) * 4; }
 
-// the row workspace of the wide forms: [R, row_stride] f32, row_stride >= V and a multiple of 4, 16-byte aligned (K28 reads float4)
-static int pointer_head_workspace(HeadArgs& a, const char* who, float* row_ws, int64_t row_stride, int64_t V) {
-  CASE_REQUIRE(row_ws && row_stride >= V && row_stride % 4 == 0 && (reinterpret_cast<uintptr_t>(row_ws) & 15) == 0,
-               "%s: the row workspace must be 16-byte aligned f32 [rows, row_stride], row_stride >= V and a multiple of 4", who);
-  a.row_ws = row_ws;
-  a.row_stride = row_stride;
-  return CASE_OK;
-}
-
-
-// the dynamic-LDS ceiling of a kernel that keeps the vocabulary row in LDS, raised once per process (``done``: the caller's static flag)
-static int pointer_head_reserve(const void* kernel, bool& done, const char* who) {
-  if (!done && hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess)
-    return case_set_error(CASE_E_LAUNCH, "%s: cannot reserve LDS", who);
-  done = true;
-  return CASE_OK;
-}
-
-// the history operands of the `_ban` forms (K32): hist [R, Tmax] int32, step t, n >= 1
+// the history operands of K32: hist [R, Tmax] int32, step t, n >= 1
 static int pointer_head_ban(BanArgs& nb, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos) {
   CASE_REQUIRE(hist && n >= 1 && t >= 0 && t < Tmax, "%s: bad history argument", who);
   if (t > NB_MAX_T) return case_set_error(CASE_E_UNSUPPORTED, "%s: the n-gram ban stages histories of up to %d tokens (step %lld)", who, NB_MAX_T, (long long)t);
@@ -1790,259 +1759,7 @@ static int pointer_head_ban(BanArgs& nb, const char* who, const int32_t* hist, i
   return CASE_OK;
 }
 
-// the wide forms take the history operands always: hist == NULL or n == 0 means no ban
-static int pointer_head_ban_opt(BanArgs& nb, bool& ban, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos) {
-  ban = hist != nullptr && n != 0;
-  nb = BanArgs();
-  return ban ? pointer_head_ban(nb, who, hist, Tmax, t, n, eos) : CASE_OK;
-}
-
-template <bool BAN, bool RULES = false>
-static int pointer_head_decode_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
-                                           const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids,
-                                           float* top, int64_t B, int64_t V, int64_t S, float* row_ws, int64_t row_stride, const typename TailArgs<RULES>::type& nb,
-                                           case_stream_t stream) {
-  CASE_REQUIRE(ids, "%s: bad argument", who);
-  HeadArgs a;
-  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S, true);
-  if (rc != CASE_OK) return rc;
-  rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
-  if (rc != CASE_OK) return rc;
-  a.ids = ids;
-  a.top = top;
-  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, true, RULES>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, nb);
-  return case_check_launch(who);
-}
-
-template <bool BAN, bool RULES = false>
-static int pointer_head_decode_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
-                                      int64_t S, const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
-  CASE_REQUIRE(ids, "%s: bad argument", who);
-  HeadArgs a;
-  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, B, V, S);
-  if (rc != CASE_OK) return rc;
-  a.ids = ids;
-  a.top = top;
-  static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_decode_kernel<BAN, false, RULES>), attr, who);
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL((pointer_head_decode_kernel<BAN, false, RULES>), dim3((unsigned)B), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, nb);
-  return case_check_launch(who);
-}
-
-extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
-                                        int64_t S, case_stream_t stream) {
-  return pointer_head_decode_launch<false>("case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S,
-                                           BanArgs(), stream);
-}
-
-extern "C" int case_pointer_head_decode_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                            const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
-                                            int64_t V, int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
-                                            case_stream_t stream) {
-  BanArgs nb;
-  const int rc = pointer_head_ban(nb, "case_pointer_head_decode_ban", hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_decode_launch<true>("case_pointer_head_decode_ban", logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S,
-                                          nb, stream);
-}
-
-extern "C" int case_pointer_head_decode_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                             const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
-                                             int64_t V, int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t,
-                                             int32_t n, int64_t eos, case_stream_t stream) {
-  const char* who = "case_pointer_head_decode_wide";
-  BanArgs nb;
-  bool ban;
-  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return ban ? pointer_head_decode_wide_launch<true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws, row_stride,
-                                                     nb, stream)
-             : pointer_head_decode_wide_launch<false>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws,
-                                                      row_stride, nb, stream);
-}
-
-template <bool BAN, bool RULES = false>
-static int pointer_head_beam_wide_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys,
-                                         const float* const* copies, const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p,
-                                         int64_t* cand_id, int64_t R, int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride,
-                                         const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
-  CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
-  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
-  HeadArgs a;
-  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S, true);
-  if (rc != CASE_OK) return rc;
-  rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, true, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, cand_p,
-                     cand_id, (int)W, nb);
-  return case_check_launch(who);
-}
-
-extern "C" int case_pointer_head_beam_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                           const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
-                                           int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
-                                           int64_t t, int32_t n, int64_t eos, case_stream_t stream) {
-  const char* who = "case_pointer_head_beam_wide";
-  BanArgs nb;
-  bool ban;
-  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return ban ? pointer_head_beam_wide_launch<true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
-                                                   row_stride, nb, stream)
-             : pointer_head_beam_wide_launch<false>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
-                                                    row_stride, nb, stream);
-}
-
-template <bool BAN, bool RULES = false>
-static int pointer_head_beam_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                    const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R, int64_t V,
-                                    int64_t S, int32_t W, const typename TailArgs<RULES>::type& nb, case_stream_t stream) {
-  CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", who);
-  if (W < 1 || W > PH_MAX_W || W > V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", who, W, PH_MAX_W);
-  HeadArgs a;
-  int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S);
-  if (rc != CASE_OK) return rc;
-  static bool attr = false;
-  rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_beam_kernel<BAN, false, RULES>), attr, who);
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL((pointer_head_beam_kernel<BAN, false, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, cand_p, cand_id,
-                     (int)W, nb);
-  return case_check_launch(who);
-}
-
-extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
-                                      int64_t V, int64_t S, int32_t W, case_stream_t stream) {
-  return pointer_head_beam_launch<false>("case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W,
-                                         BanArgs(), stream);
-}
-
-extern "C" int case_pointer_head_beam_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                          const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
-                                          int64_t V, int64_t S, int32_t W, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
-                                          case_stream_t stream) {
-  BanArgs nb;
-  const int rc = pointer_head_ban(nb, "case_pointer_head_beam_ban", hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_beam_launch<true>("case_pointer_head_beam_ban", logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S,
-                                        W, nb, stream);
-}
-
-template <bool BAN, bool WIDE = false, bool RULES = false>
-static int pointer_head_sample_launch(const char* who, const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                      const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
-                                      uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
-                                      float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad,
-                                      int32_t first, int32_t last, const typename TailArgs<RULES>::type& nb, case_stream_t stream, float* row_ws = nullptr,
-                                      int64_t row_stride = 0) {
-  CASE_REQUIRE(ids && prob && ended && R > 0 && V > 0 && R < (1ll << 31), "%s: bad argument", who);
-  CASE_REQUIRE(temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f, "%s: temperature must be > 0, top_k >= 0 and top_p in (0, 1]", who);
-  CASE_REQUIRE((logits != nullptr) != (dist_in != nullptr), "%s: give either the logits or a ready distribution", who);
-  HeadArgs a;
-  if (logits) {
-    const int rc = pointer_head_args(a, who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, R, V, S, WIDE);
-    if (rc != CASE_OK) return rc;
-  } else {
-    const int64_t max_v = WIDE ? PW_MAX_DIST_V : PH_MAX_V;
-    if (V > max_v) return case_set_error(CASE_E_UNSUPPORTED, "%s: built for V <= %lld", who, (long long)max_v);
-    a = HeadArgs();
-    a.dist = dist;
-    a.V = V;
-  }
-  if constexpr (WIDE) {
-    // a ready distribution is read where it lies when its rows are 16-byte aligned and nothing is to be zeroed in them
-    const bool in_place = !logits && !BAN && V % 4 == 0 && (reinterpret_cast<uintptr_t>(dist_in) & 15) == 0;
-    if (!in_place) {
-      const int rc = pointer_head_workspace(a, who, row_ws, row_stride, V);
-      if (rc != CASE_OK) return rc;
-    }
-  }
-  SampleArgs s;
-  s.dist_in = dist_in;
-  s.uniforms = uniforms;
-  s.state = state;
-  s.seed = seed;
-  s.offset = offset;
-  s.ended = ended;
-  s.ids = ids;
-  s.prob = prob;
-  s.eos = eos;
-  s.unk = unk;
-  s.pad = pad;
-  s.temperature = temperature;
-  s.top_p = top_p;
-  s.top_k = top_k;
-  s.first = first;
-  s.last = last;
-  if constexpr (WIDE) {
-    hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, true, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(0), (hipStream_t)stream, a, s, nb);
-    return case_check_launch(who);
-  }
-  static bool attr = false;
-  const int rc = pointer_head_reserve(reinterpret_cast<const void*>(&pointer_head_sample_kernel<BAN, false, RULES>), attr, who);
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL((pointer_head_sample_kernel<BAN, false, RULES>), dim3((unsigned)R), dim3(PH_THREADS), pointer_head_lds(V), (hipStream_t)stream, a, s, nb);
-  return case_check_launch(who);
-}
-
-extern "C" int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
-                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
-                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
-                                        int64_t pad, int32_t first, int32_t last, case_stream_t stream) {
-  return pointer_head_sample_launch<false>("case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob,
-                                           ended, uniforms, R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last,
-                                           BanArgs(), stream);
-}
-
-extern "C" int case_pointer_head_sample_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                            const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
-                                            float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
-                                            int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
-                                            int64_t unk, int64_t pad, int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
-                                            case_stream_t stream) {
-  BanArgs nb;
-  const int rc = pointer_head_ban(nb, "case_pointer_head_sample_ban", hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_sample_launch<true>("case_pointer_head_sample_ban", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob,
-                                          ended, uniforms, R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb,
-                                          stream);
-}
-
-extern "C" int case_pointer_head_sample_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
-                                             const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
-                                             float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
-                                             int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
-                                             int64_t unk, int64_t pad, int32_t first, int32_t last, float* row_ws, int64_t row_stride, int32_t* hist,
-                                             int64_t Tmax, int64_t t, int32_t n, case_stream_t stream) {
-  const char* who = "case_pointer_head_sample_wide";
-  BanArgs nb;
-  bool ban;
-  const int rc = pointer_head_ban_opt(nb, ban, who, hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  return ban ? pointer_head_sample_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
-                                                      R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
-                                                      row_ws, row_stride)
-             : pointer_head_sample_launch<false, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
-                                                       R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
-                                                       row_ws, row_stride);
-}
-
-// K32 as a launch of its own (the unfused head): one wave per row zeroes the banned entries of dist [R, V] in place
-extern "C" int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n,
-                              int64_t eos, case_stream_t stream) {
-  CASE_REQUIRE(dist && R > 0 && R < (1ll << 31) && V > 0, "case_ngram_ban: bad argument");
-  BanArgs nb;
-  const int rc = pointer_head_ban(nb, "case_ngram_ban", hist, Tmax, t, n, eos);
-  if (rc != CASE_OK) return rc;
-  hipLaunchKernelGGL(ngram_ban_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, dist, ended, V, nb);
-  return case_check_launch("case_ngram_ban");
-}
-
-// ---- the decoding rules (CASE_FEAT_DECODE_RULES): the `_rules` forms of the heads and case_row_rules ------------------------------------------------
+// the operands of the decoding rules (CASE_FEAT_DECODE_RULES)
 static int pointer_head_rule_args(RuleArgs& rl, const char* who, int64_t rows, int64_t t, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
                                   int64_t banned_stride, int64_t rows_per_item) {
   CASE_REQUIRE(t >= 0 && t < (1ll << 31) && min_length >= 0 && K >= 0 && (K == 0 || banned) && rows_per_item >= 1 &&
@@ -2059,15 +1776,180 @@ static int pointer_head_rule_args(RuleArgs& rl, const char* who, int64_t rows, i
   return CASE_OK;
 }
 
-// the ban's operands (hist == NULL or n == 0: no ban, as in the wide forms) and the rules into one kernel argument
-static int pointer_head_rules(RuleBanArgs& nb, const char* who, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t rows,
-                              int64_t eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item) {
+// ---- one call of a fused head (K23 argmax, K24 top-W, K28 draw), as any of their 15 entry points states it -------------------------------------
+// The entry points differ in which of the optional parts they carry; what a head kind adds (its outputs, W, the draw) goes to its launcher.
+struct HeadWorkspace {  // the row of a `_wide` form: [R, stride] f32 in device memory
+  float* ws;
+  int64_t stride;
+};
+struct HeadHistory {  // K32's operands; hist == NULL or n == 0 means no ban unless the entry point (a `_ban` form) requires one
+  const int32_t* hist;
+  int64_t Tmax, t;
+  int32_t n;
+  int64_t eos;
+  bool required;
+};
+struct HeadRules {  // the operands of a `_rules` form (which always brings a HeadHistory: the step t is there)
+  int64_t eos;
+  int32_t min_length;
+  const int32_t* banned;
+  int32_t K;
+  int64_t banned_stride, rows_per_item;
+};
+struct HeadCall {
+  const char* who;
+  // the row source: the operands of the row build, or (K28 alone, logits null) a ready distribution
+  const float *logits, *mix_logits;
+  const uint32_t* keys;
+  const float* const* copies;
+  const int64_t* lens;
+  int32_t nmem;
+  const float* dist_in;
+  float *gen, *dist;  // each [R, V] or null
+  int64_t R, V, S;
+  case_stream_t stream;
+  const HeadWorkspace* wide;  // null: the row in LDS (V <= 36 000)
+  const HeadHistory* ban;     // null: the entry point takes no history
+  const HeadRules* rules;     // null: the entry point takes no rules
+};
+
+// the history and the rules as the kernels' trailing argument (the instances without rules take its BanArgs part); ban: a history is applied
+static int pointer_head_tail(const HeadCall& c, RuleBanArgs& nb, bool& ban) {
   nb = RuleBanArgs();
-  if (hist != nullptr && n != 0) {
-    const int rc = pointer_head_ban(nb, who, hist, Tmax, t, n, ban_eos);
+  ban = c.ban && (c.ban->required || (c.ban->hist != nullptr && c.ban->n != 0));
+  if (ban)
+    if (const int rc = pointer_head_ban(nb, c.who, c.ban->hist, c.ban->Tmax, c.ban->t, c.ban->n, c.ban->eos)) return rc;
+  if (!c.rules) return CASE_OK;
+  const HeadRules& r = *c.rules;
+  return pointer_head_rule_args(nb.rl, c.who, c.R, c.ban->t, r.eos, r.min_length, r.banned, r.K, r.banned_stride, r.rows_per_item);
+}
+
+// the row's operands: built from the logits or (`dist_in`) read as it is; the wide forms' workspace [R, row_stride] f32, row_stride >= V and a
+// multiple of 4, 16-byte aligned (K28 reads float4), unless the row is read where it lies
+static int pointer_head_row(const HeadCall& c, HeadArgs& a, bool in_place = false) {
+  a = HeadArgs();
+  if (!c.dist_in) {
+    const int rc = pointer_head_fill(a, c.who, c.logits, c.mix_logits, c.keys, c.copies, c.lens, c.nmem, c.R, c.V, c.S, c.wide ? PS_MAX_V : PH_MAX_V,
+                                     c.wide ? "" : " (run the softmax / scatter / argmax launches)");
     if (rc != CASE_OK) return rc;
+    a.gen = c.gen;
+  } else {
+    const int64_t max_v = c.wide ? PW_MAX_DIST_V : PH_MAX_V;
+    if (c.V > max_v) return case_set_error(CASE_E_UNSUPPORTED, "%s: built for V <= %lld", c.who, (long long)max_v);
+    a.V = c.V;
   }
-  return pointer_head_rule_args(nb.rl, who, rows, t, eos, min_length, banned, K, banned_stride, rows_per_item);
+  a.dist = c.dist;
+  if (!c.wide || in_place) return CASE_OK;
+  CASE_REQUIRE(c.wide->ws && c.wide->stride >= c.V && c.wide->stride % 4 == 0 && (reinterpret_cast<uintptr_t>(c.wide->ws) & 15) == 0,
+               "%s: the row workspace must be 16-byte aligned f32 [rows, row_stride], row_stride >= V and a multiple of 4", c.who);
+  a.row_ws = c.wide->ws;
+  a.row_stride = c.wide->stride;
+  return CASE_OK;
+}
+
+// The three runtime flags as compile-time constants for a generic lambda: the six instances every head kernel has.
+//   plain <false, false, false>   `_ban` <true, false, false>   `_wide` <ban given, true, false>   `_rules` <true, false, true>   `_wide_rules` <true, true, true>
+// (the rules instances take n = 0 for "no ban", so there is no <false, *, true>)
+template <typename F>
+static int pointer_head_pick(bool ban, bool wide, bool rules, F&& f) {
+  constexpr std::true_type yes{};
+  constexpr std::false_type no{};
+  if (rules) return wide ? f(yes, yes, yes) : f(yes, no, yes);
+  if (wide) return ban ? f(yes, yes, no) : f(no, yes, no);
+  return ban ? f(yes, no, no) : f(no, no, no);
+}
+
+// One workgroup per row.  An instance that keeps the vocabulary row in LDS has its dynamic-LDS ceiling raised once per process.
+template <auto KERNEL, bool WIDE, typename... Args>
+static int pointer_head_launch(const HeadCall& c, const Args&... args) {
+  if constexpr (!WIDE) {
+    static bool reserved = false;
+    if (!reserved && hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, 158 * 1024) != hipSuccess)
+      return case_set_error(CASE_E_LAUNCH, "%s: cannot reserve LDS", c.who);
+    reserved = true;
+  }
+  hipLaunchKernelGGL(KERNEL, dim3((unsigned)c.R), dim3(PH_THREADS), pointer_head_lds(WIDE ? 0 : c.V), (hipStream_t)c.stream, args...);
+  return case_check_launch(c.who);
+}
+
+// K23
+static int pointer_head_argmax(const HeadCall& c, int64_t* ids, float* top) {
+  RuleBanArgs nb;
+  bool ban;
+  if (const int rc = pointer_head_tail(c, nb, ban)) return rc;
+  CASE_REQUIRE(ids, "%s: bad argument", c.who);
+  HeadArgs a;
+  if (const int rc = pointer_head_row(c, a)) return rc;
+  a.ids = ids;
+  a.top = top;
+  return pointer_head_pick(ban, c.wide != nullptr, c.rules != nullptr, [&](auto BAN, auto WIDE, auto RULES) {
+    return pointer_head_launch<&pointer_head_decode_kernel<BAN(), WIDE(), RULES()>, WIDE()>(c, a, nb);
+  });
+}
+
+// K24
+static int pointer_head_top(const HeadCall& c, float* cand_p, int64_t* cand_id, int32_t W) {
+  RuleBanArgs nb;
+  bool ban;
+  if (const int rc = pointer_head_tail(c, nb, ban)) return rc;
+  CASE_REQUIRE(cand_p && cand_id, "%s: bad argument", c.who);
+  if (W < 1 || W > PH_MAX_W || W > c.V) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. min(%d, V)", c.who, W, PH_MAX_W);
+  HeadArgs a;
+  if (const int rc = pointer_head_row(c, a)) return rc;
+  return pointer_head_pick(ban, c.wide != nullptr, c.rules != nullptr, [&](auto BAN, auto WIDE, auto RULES) {
+    return pointer_head_launch<&pointer_head_beam_kernel<BAN(), WIDE(), RULES()>, WIDE()>(c, a, cand_p, cand_id, (int)W, nb);
+  });
+}
+
+// K28 (s.dist_in is the call's)
+static int pointer_head_draw(const HeadCall& c, SampleArgs s) {
+  RuleBanArgs nb;
+  bool ban;
+  if (const int rc = pointer_head_tail(c, nb, ban)) return rc;
+  CASE_REQUIRE(s.ids && s.prob && s.ended && c.R > 0 && c.V > 0 && c.R < (1ll << 31), "%s: bad argument", c.who);
+  CASE_REQUIRE(s.temperature > 0.f && s.top_k >= 0 && s.top_p > 0.f && s.top_p <= 1.f, "%s: temperature must be > 0, top_k >= 0 and top_p in (0, 1]", c.who);
+  CASE_REQUIRE((c.logits != nullptr) != (c.dist_in != nullptr), "%s: give either the logits or a ready distribution", c.who);
+  // the wide form reads a ready distribution where it lies when its rows are 16-byte aligned and nothing is to be zeroed in them
+  const bool in_place = c.wide && !c.logits && !ban && !c.rules && c.V % 4 == 0 && (reinterpret_cast<uintptr_t>(c.dist_in) & 15) == 0;
+  HeadArgs a;
+  if (const int rc = pointer_head_row(c, a, in_place)) return rc;
+  s.dist_in = c.dist_in;
+  return pointer_head_pick(ban, c.wide != nullptr, c.rules != nullptr, [&](auto BAN, auto WIDE, auto RULES) {
+    return pointer_head_launch<&pointer_head_sample_kernel<BAN(), WIDE(), RULES()>, WIDE()>(c, a, s, nb);
+  });
+}
+
+static SampleArgs sample_args(int64_t* ids, float* prob, uint8_t* ended, const float* uniforms, float temperature, int32_t top_k, float top_p,
+                              uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk, int64_t pad, int32_t first,
+                              int32_t last) {
+  // (the fields in SampleArgs' order; dist_in is the call's)
+  return {nullptr, uniforms, state, seed, offset, ended, ids, prob, eos, unk, pad, temperature, top_p, top_k, first, last};
+}
+
+// ---- the 15 entry points: each states its call and hands it to its head's launcher --------------------------------------------------------------
+extern "C" int case_pointer_head_decode(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B, int64_t V,
+                                        int64_t S, case_stream_t stream) {
+  return pointer_head_argmax({"case_pointer_head_decode", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, B, V, S, stream}, ids, top);
+}
+
+extern "C" int case_pointer_head_decode_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                            const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                            int64_t V, int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                            case_stream_t stream) {
+  const HeadHistory ban = {hist, Tmax, t, n, eos, true};
+  return pointer_head_argmax({"case_pointer_head_decode_ban", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, B, V, S, stream, nullptr, &ban},
+                             ids, top);
+}
+
+extern "C" int case_pointer_head_decode_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                             const int64_t* lens, int32_t nmem, float* gen, float* dist, int64_t* ids, float* top, int64_t B,
+                                             int64_t V, int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t,
+                                             int32_t n, int64_t eos, case_stream_t stream) {
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, eos, false};
+  return pointer_head_argmax({"case_pointer_head_decode_wide", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, B, V, S, stream, &ws, &ban},
+                             ids, top);
 }
 
 extern "C" int case_pointer_head_decode_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2075,11 +1957,10 @@ extern "C" int case_pointer_head_decode_rules(const float* logits, const float* 
                                               int64_t V, int64_t S, int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos, int64_t eos,
                                               int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride, int64_t rows_per_item,
                                               case_stream_t stream) {
-  const char* who = "case_pointer_head_decode_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, B, eos, min_length, banned, K, banned_stride, rows_per_item);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_decode_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, nb, stream);
+  const HeadHistory ban = {hist, Tmax, t, n, ban_eos, false};
+  const HeadRules rules = {eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_argmax(
+      {"case_pointer_head_decode_rules", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, B, V, S, stream, nullptr, &ban, &rules}, ids, top);
 }
 
 extern "C" int case_pointer_head_decode_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2087,12 +1968,36 @@ extern "C" int case_pointer_head_decode_wide_rules(const float* logits, const fl
                                                    int64_t V, int64_t S, float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t,
                                                    int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
                                                    int64_t banned_stride, int64_t rows_per_item, case_stream_t stream) {
-  const char* who = "case_pointer_head_decode_wide_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, B, eos, min_length, banned, K, banned_stride, rows_per_item);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_decode_wide_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, ids, top, B, V, S, row_ws, row_stride,
-                                                     nb, stream);
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, ban_eos, false};
+  const HeadRules rules = {eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_argmax(
+      {"case_pointer_head_decode_wide_rules", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, B, V, S, stream, &ws, &ban, &rules}, ids, top);
+}
+
+extern "C" int case_pointer_head_beam(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                      const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                      int64_t V, int64_t S, int32_t W, case_stream_t stream) {
+  return pointer_head_top({"case_pointer_head_beam", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, R, V, S, stream}, cand_p, cand_id, W);
+}
+
+extern "C" int case_pointer_head_beam_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                          const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                          int64_t V, int64_t S, int32_t W, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t eos,
+                                          case_stream_t stream) {
+  const HeadHistory ban = {hist, Tmax, t, n, eos, true};
+  return pointer_head_top({"case_pointer_head_beam_ban", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, R, V, S, stream, nullptr, &ban},
+                          cand_p, cand_id, W);
+}
+
+extern "C" int case_pointer_head_beam_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                           const int64_t* lens, int32_t nmem, float* gen, float* dist, float* cand_p, int64_t* cand_id, int64_t R,
+                                           int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
+                                           int64_t t, int32_t n, int64_t eos, case_stream_t stream) {
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, eos, false};
+  return pointer_head_top({"case_pointer_head_beam_wide", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, R, V, S, stream, &ws, &ban},
+                          cand_p, cand_id, W);
 }
 
 extern "C" int case_pointer_head_beam_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2100,11 +2005,11 @@ extern "C" int case_pointer_head_beam_rules(const float* logits, const float* mi
                                             int64_t V, int64_t S, int32_t W, const int32_t* hist, int64_t Tmax, int64_t t, int32_t n, int64_t ban_eos,
                                             int64_t eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
                                             int64_t rows_per_item, case_stream_t stream) {
-  const char* who = "case_pointer_head_beam_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, R, eos, min_length, banned, K, banned_stride, rows_per_item);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_beam_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, nb, stream);
+  const HeadHistory ban = {hist, Tmax, t, n, ban_eos, false};
+  const HeadRules rules = {eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_top(
+      {"case_pointer_head_beam_rules", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, R, V, S, stream, nullptr, &ban, &rules}, cand_p,
+      cand_id, W);
 }
 
 extern "C" int case_pointer_head_beam_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2112,12 +2017,45 @@ extern "C" int case_pointer_head_beam_wide_rules(const float* logits, const floa
                                                  int64_t V, int64_t S, int32_t W, float* row_ws, int64_t row_stride, const int32_t* hist, int64_t Tmax,
                                                  int64_t t, int32_t n, int64_t ban_eos, int64_t eos, int32_t min_length, const int32_t* banned, int32_t K,
                                                  int64_t banned_stride, int64_t rows_per_item, case_stream_t stream) {
-  const char* who = "case_pointer_head_beam_wide_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, ban_eos, R, eos, min_length, banned, K, banned_stride, rows_per_item);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_beam_wide_launch<true, true>(who, logits, mix_logits, keys, copies, lens, nmem, gen, dist, cand_p, cand_id, R, V, S, W, row_ws,
-                                                   row_stride, nb, stream);
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, ban_eos, false};
+  const HeadRules rules = {eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_top(
+      {"case_pointer_head_beam_wide_rules", logits, mix_logits, keys, copies, lens, nmem, nullptr, gen, dist, R, V, S, stream, &ws, &ban, &rules}, cand_p,
+      cand_id, W);
+}
+
+// K28: the history's `eos` is the loop's; the rules bring their own (`rule_eos`)
+extern "C" int case_pointer_head_sample(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                        const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids, float* prob,
+                                        uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature, int32_t top_k,
+                                        float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos, int64_t unk,
+                                        int64_t pad, int32_t first, int32_t last, case_stream_t stream) {
+  return pointer_head_draw({"case_pointer_head_sample", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, R, V, S, stream},
+                           sample_args(ids, prob, ended, uniforms, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last));
+}
+
+extern "C" int case_pointer_head_sample_ban(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                            const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                            float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
+                                            int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
+                                            int64_t unk, int64_t pad, int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
+                                            case_stream_t stream) {
+  const HeadHistory ban = {hist, Tmax, t, n, eos, true};
+  return pointer_head_draw({"case_pointer_head_sample_ban", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, R, V, S, stream, nullptr, &ban},
+                           sample_args(ids, prob, ended, uniforms, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last));
+}
+
+extern "C" int case_pointer_head_sample_wide(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
+                                             const int64_t* lens, int32_t nmem, const float* dist_in, float* gen, float* dist, int64_t* ids,
+                                             float* prob, uint8_t* ended, const float* uniforms, int64_t R, int64_t V, int64_t S, float temperature,
+                                             int32_t top_k, float top_p, uint64_t seed, uint64_t offset, const CaseStepState* state, int64_t eos,
+                                             int64_t unk, int64_t pad, int32_t first, int32_t last, float* row_ws, int64_t row_stride, int32_t* hist,
+                                             int64_t Tmax, int64_t t, int32_t n, case_stream_t stream) {
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, eos, false};
+  return pointer_head_draw({"case_pointer_head_sample_wide", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, R, V, S, stream, &ws, &ban},
+                           sample_args(ids, prob, ended, uniforms, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last));
 }
 
 extern "C" int case_pointer_head_sample_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2127,12 +2065,11 @@ extern "C" int case_pointer_head_sample_rules(const float* logits, const float* 
                                               int64_t unk, int64_t pad, int32_t first, int32_t last, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
                                               int64_t rule_eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
                                               int64_t rows_per_item, case_stream_t stream) {
-  const char* who = "case_pointer_head_sample_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, eos, R, rule_eos, min_length, banned, K, banned_stride, rows_per_item);
-  if (rc != CASE_OK) return rc;
-  return pointer_head_sample_launch<true, false, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
-                                                       R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream);
+  const HeadHistory ban = {hist, Tmax, t, n, eos, false};
+  const HeadRules rules = {rule_eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_draw(
+      {"case_pointer_head_sample_rules", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, R, V, S, stream, nullptr, &ban, &rules},
+      sample_args(ids, prob, ended, uniforms, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last));
 }
 
 extern "C" int case_pointer_head_sample_wide_rules(const float* logits, const float* mix_logits, const uint32_t* keys, const float* const* copies,
@@ -2143,13 +2080,23 @@ extern "C" int case_pointer_head_sample_wide_rules(const float* logits, const fl
                                                    float* row_ws, int64_t row_stride, int32_t* hist, int64_t Tmax, int64_t t, int32_t n,
                                                    int64_t rule_eos, int32_t min_length, const int32_t* banned, int32_t K, int64_t banned_stride,
                                                    int64_t rows_per_item, case_stream_t stream) {
-  const char* who = "case_pointer_head_sample_wide_rules";
-  RuleBanArgs nb;
-  const int rc = pointer_head_rules(nb, who, hist, Tmax, t, n, eos, R, rule_eos, min_length, banned, K, banned_stride, rows_per_item);
+  const HeadWorkspace ws = {row_ws, row_stride};
+  const HeadHistory ban = {hist, Tmax, t, n, eos, false};
+  const HeadRules rules = {rule_eos, min_length, banned, K, banned_stride, rows_per_item};
+  return pointer_head_draw(
+      {"case_pointer_head_sample_wide_rules", logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, R, V, S, stream, &ws, &ban, &rules},
+      sample_args(ids, prob, ended, uniforms, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last));
+}
+
+// K32 as a launch of its own (the unfused head): one wave per row zeroes the banned entries of dist [R, V] in place
+extern "C" int case_ngram_ban(float* dist, const int32_t* hist, const uint8_t* ended, int64_t R, int64_t V, int64_t Tmax, int64_t t, int32_t n,
+                              int64_t eos, case_stream_t stream) {
+  CASE_REQUIRE(dist && R > 0 && R < (1ll << 31) && V > 0, "case_ngram_ban: bad argument");
+  BanArgs nb;
+  const int rc = pointer_head_ban(nb, "case_ngram_ban", hist, Tmax, t, n, eos);
   if (rc != CASE_OK) return rc;
-  return pointer_head_sample_launch<true, true, true>(who, logits, mix_logits, keys, copies, lens, nmem, dist_in, gen, dist, ids, prob, ended, uniforms,
-                                                      R, V, S, temperature, top_k, top_p, seed, offset, state, eos, unk, pad, first, last, nb, stream,
-                                                      row_ws, row_stride);
+  hipLaunchKernelGGL(ngram_ban_kernel, dim3((unsigned)R), dim3(64), 0, (hipStream_t)stream, dist, ended, V, nb);
+  return case_check_launch("case_ngram_ban");
 }
 
 // the rules as a launch of their own (the unfused head): one wave per row zeroes the entries of dist [R, V] in place

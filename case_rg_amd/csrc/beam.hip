@@ -235,47 +235,55 @@ __global__ __launch_bounds__(64) void beam_backtrack_kernel(const int32_t* __res
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
+// K25's three entry points share one check and one launch.  `flat`: the entry point takes the flat-history pair (required then); `alpha`: the length
+// penalty, or null for the plain key.  `who` names the entry point in every message.
+static int beam_advance_launch(const char* who, const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
+                               int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step, int32_t* fin_slot,
+                               int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, bool flat, const int32_t* flat_old, int32_t* flat_new,
+                               int64_t Tmax, const float* alpha, case_stream_t stream) {
+  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
+                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T &&
+                   (!flat || (flat_old && flat_new && flat_old != flat_new && t < Tmax)),
+               "%s: bad argument", who);
+  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "%s: width %d outside 1 .. %d", who, W, BEAM_MAX_W);
+  const auto launch = [&](auto kernel, auto... tail) {
+    hipLaunchKernelGGL(kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token, hist_parent,
+                       hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax, tail...);
+  };
+  if (alpha)
+    launch(beam_advance_alpha_kernel, *alpha);
+  else if (flat)
+    launch(beam_advance_kernel<true>);
+  else
+    launch(beam_advance_kernel<false>);
+  return case_check_launch(who);
+}
+
 extern "C" int case_beam_advance(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
                                  int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step,
                                  int32_t* fin_slot, int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, case_stream_t stream) {
-  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
-                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T,
-               "case_beam_advance: bad argument");
-  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance: width %d outside 1 .. %d", W, BEAM_MAX_W);
-  hipLaunchKernelGGL(beam_advance_kernel<false>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
-                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, nullptr, nullptr, (int64_t)0);
-  return case_check_launch("case_beam_advance");
+  return beam_advance_launch("case_beam_advance", cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot, t,
+                             T, B, W, eos, false, nullptr, nullptr, 0, nullptr, stream);
 }
 
 extern "C" int case_beam_advance_ban(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
                                      int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step,
                                      int32_t* fin_slot, int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, const int32_t* flat_old,
                                      int32_t* flat_new, int64_t Tmax, case_stream_t stream) {
-  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
-                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T && flat_old && flat_new && flat_old != flat_new && t < Tmax,
-               "case_beam_advance_ban: bad argument");
-  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance_ban: width %d outside 1 .. %d", W, BEAM_MAX_W);
-  hipLaunchKernelGGL(beam_advance_kernel<true>, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
-                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax);
-  return case_check_launch("case_beam_advance_ban");
+  return beam_advance_launch("case_beam_advance_ban", cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot,
+                             t, T, B, W, eos, true, flat_old, flat_new, Tmax, nullptr, stream);
 }
 
-// K25 with the length penalty alpha (CASE_FEAT_DECODE_RULES): the flat-history form; alpha == 1 is case_beam_advance_ban's launch itself
+// K25 with the length penalty alpha (CASE_FEAT_DECODE_RULES): the flat-history form; alpha == 1 is case_beam_advance_ban's call itself
 extern "C" int case_beam_advance_rules(const float* cand_p, const int64_t* cand_id, uint8_t* alive, float* cum, int32_t* len, int32_t* parent,
                                        int64_t* token, int32_t* hist_parent, int64_t* hist_token, float* fin_key, int32_t* fin_step,
                                        int32_t* fin_slot, int64_t t, int64_t T, int64_t B, int32_t W, int64_t eos, const int32_t* flat_old,
                                        int32_t* flat_new, int64_t Tmax, float length_penalty, case_stream_t stream) {
   CASE_REQUIRE(length_penalty >= 0.f && length_penalty < INFINITY, "case_beam_advance_rules: the length penalty must be a finite float >= 0");
-  if (length_penalty == 1.f)
-    return case_beam_advance_ban(cand_p, cand_id, alive, cum, len, parent, token, hist_parent, hist_token, fin_key, fin_step, fin_slot, t, T, B, W, eos,
-                                 flat_old, flat_new, Tmax, stream);
-  CASE_REQUIRE(cand_p && cand_id && alive && cum && len && parent && token && hist_parent && hist_token && fin_key && fin_step && fin_slot &&
-                   B > 0 && B < (1ll << 31) && T > 0 && T < (1ll << 30) && t >= 0 && t < T && flat_old && flat_new && flat_old != flat_new && t < Tmax,
-               "case_beam_advance_rules: bad argument");
-  if (W < 1 || W > BEAM_MAX_W) return case_set_error(CASE_E_UNSUPPORTED, "case_beam_advance_rules: width %d outside 1 .. %d", W, BEAM_MAX_W);
-  hipLaunchKernelGGL(beam_advance_alpha_kernel, dim3((unsigned)B), dim3(64), 0, (hipStream_t)stream, cand_p, cand_id, alive, cum, len, parent, token,
-                     hist_parent, hist_token, fin_key, fin_step, fin_slot, (int)t, (int)T, B, (int)W, eos, flat_old, flat_new, Tmax, length_penalty);
-  return case_check_launch("case_beam_advance_rules");
+  const bool plain = length_penalty == 1.f;
+  return beam_advance_launch(plain ? "case_beam_advance_ban" : "case_beam_advance_rules", cand_p, cand_id, alive, cum, len, parent, token, hist_parent,
+                             hist_token, fin_key, fin_step, fin_slot, t, T, B, W, eos, true, flat_old, flat_new, Tmax, plain ? nullptr : &length_penalty,
+                             stream);
 }
 
 extern "C" int case_beam_gather(const void* const* src, void* const* dst, int32_t nlayers, const int32_t* parent, const uint8_t* valid_src,

@@ -1997,11 +1997,6 @@ def _row_workspace(rows, V, dev):
     return torch.empty(rows, stride, dtype=torch.float32, device=dev), stride
 
 
-def _ban_operands_wide(ban, rows, who):
-    """The history operands of a wide entry point: those of ``_ban_operands``, or (NULL, 0, 0, 0, -1) for no ban."""
-    return (None, 0, 0, 0, -1) if ban is None else _ban_operands(ban, rows, who)
-
-
 LINEAR_SKINNY = os.environ.get("CASE_LINEAR_SKINNY", "auto")  # "off": torch.cat + the GEMM path (A/B)
 
 
@@ -2080,14 +2075,18 @@ def _head_operands(logits, mix_logits, source_map, copies):
     return logits, mix_logits, cs, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, source_map.keys.shape[1]
 
 
-def _ban_operands(ban, rows, who):
-    """``ban`` = (hist int32 [rows, Tmax] contiguous, t, n, eos | None) -> the trailing arguments of a ``_ban`` entry point (K32)."""
-    hist, t, n, eos = ban
+NGRAM_MAX_T = 256  # K32 stages a history in LDS (beside the vocabulary row in the LDS heads); K33 and the n-gram metrics stage rows as long
+
+
+def _ban_operands(ban, rows, who, own_eos=True):
+    """``ban`` = (hist int32 [rows, Tmax] contiguous, t, n, eos | None) -> the history operands of an entry point (K32): hist, Tmax, t, n, eos.
+    ``own_eos=False`` (the sampler, whose loop's ``eos`` serves): ``ban`` = (hist, t, n) and no eos operand."""
+    (hist, t, n, eos) = ban if own_eos else tuple(ban) + (None,)
     if hist.dtype != torch.int32 or hist.dim() != 2 or hist.shape[0] != rows or not hist.is_contiguous():
         raise TypeError("%s: the history must be a contiguous int32 [%d, Tmax]" % (who, rows))
     if int(n) < 1 or not 0 <= int(t) < hist.shape[1] or int(t) > NGRAM_MAX_T:
         raise ValueError("%s: n >= 1 and 0 <= t < min(Tmax, %d + 1) (got n %r, t %r, Tmax %d)" % (who, NGRAM_MAX_T, n, t, hist.shape[1]))
-    return _ptr(hist), hist.shape[1], int(t), int(n), -1 if eos is None else int(eos)
+    return (_ptr(hist), hist.shape[1], int(t), int(n)) + ((-1 if eos is None else int(eos),) if own_eos else ())
 
 
 # The decoding rules on the mixed distribution row (behind K32, before the argmax / top-W / draw): ``min_length`` zeroes row[eos] while
@@ -2111,13 +2110,19 @@ def row_rules(eos, min_length=0, banned=None, rows_per_item=1, t=0):
     if min_length < 0 or rows_per_item < 1:
         raise ValueError("row_rules: min_length >= 0 and rows_per_item >= 1 (got %d, %d)" % (min_length, rows_per_item))
     if banned is not None:
-        if not torch.is_tensor(banned) or banned.dtype != torch.int32 or banned.dim() not in (1, 2) or not banned.is_contiguous():
-            raise TypeError("row_rules: banned must be a contiguous int32 tensor [K] or [items, K]")
-        if banned.shape[-1] > RULES_MAX_BANNED:
-            raise ValueError("row_rules: at most %d banned ids per item (got %d)" % (RULES_MAX_BANNED, banned.shape[-1]))
+        _check_banned(banned, "row_rules")
         if banned.numel() == 0:
             banned = None
     return RowRules(-1 if eos is None else int(eos), int(t), min_length, banned, rows_per_item)
+
+
+def _check_banned(banned, who):
+    """``banned`` is an int32 tensor [K] or [items, K] the kernels can read, K <= RULES_MAX_BANNED -> K."""
+    if not torch.is_tensor(banned) or banned.dtype != torch.int32 or banned.dim() not in (1, 2) or not banned.is_contiguous():
+        raise TypeError("%s: banned must be a contiguous int32 tensor [K] or [items, K]" % who)
+    if banned.shape[-1] > RULES_MAX_BANNED:
+        raise ValueError("%s: at most %d banned ids per item (got %d)" % (who, RULES_MAX_BANNED, banned.shape[-1]))
+    return banned.shape[-1]
 
 
 def _rule_operands(rules, rows, who):
@@ -2129,11 +2134,7 @@ def _rule_operands(rules, rows, who):
         raise ValueError("%s: t >= 0, min_length >= 0 and rows_per_item >= 1 (got %r, %r, %r)" % (who, t, min_length, rpi))
     K = stride = 0
     if banned is not None:
-        if banned.dtype != torch.int32 or banned.dim() not in (1, 2) or not banned.is_contiguous():
-            raise TypeError("%s: banned must be a contiguous int32 tensor [K] or [items, K]" % who)
-        K = banned.shape[-1]
-        if K > RULES_MAX_BANNED:
-            raise ValueError("%s: at most %d banned ids per item (got %d)" % (who, RULES_MAX_BANNED, K))
+        K = _check_banned(banned, who)
         if banned.dim() == 2:
             if rows % int(rpi) or banned.shape[0] * int(rpi) != rows:
                 raise ValueError("%s: %d rows, %d lists, rows_per_item %d" % (who, rows, banned.shape[0], rpi))
@@ -2141,14 +2142,24 @@ def _rule_operands(rules, rows, who):
     return int(t), (int(eos), int(min_length), _ptr(banned) if K else None, K, stride, int(rpi))
 
 
-def _ban_operands_rules(ban, t, rows, who):
-    """The history operands of a ``_rules`` entry point at step ``t``: those of ``_ban_operands``, or no ban (NULL, 0, t, 0, -1)."""
-    if ban is None:
-        return (None, 0, t, 0, -1)
-    out = _ban_operands(ban, rows, who)
-    if out[2] != t:
-        raise ValueError("%s: the ban's step %d and the rules' step %d differ" % (who, out[2], t))
-    return out
+def head_entry(head, row, has_ban, has_rules):
+    """The C entry point of a fused head call: ``head`` "decode" (K23) | "beam" (K24) | "sample" (K28), ``row`` "lds" | "global"."""
+    return "case_pointer_head_" + head + ("_wide" if row == "global" else "") + ("_rules" if has_rules else "_ban" if has_ban and row == "lds" else "")
+
+
+def _head_tail(head, row, ban, rules, rows, V, dev, who, own_eos=True, in_place=False):
+    """What follows a head's own operands: -> (the entry point's name, its trailing operands up to the stream, the row workspace to keep alive
+    until the call returns).  The tail is the workspace and its stride (a global row; NULL, 0 for a row read ``in_place``), the history
+    operands (``_ban_operands``; NULL with n = 0 where the entry point takes them and there is no ban) and the rule operands."""
+    t, rule = _rule_operands(rules, rows, who) if rules is not None else (0, ())
+    if ban is not None:
+        hist = _ban_operands(ban, rows, who, own_eos)
+        if rules is not None and hist[2] != t:
+            raise ValueError("%s: the ban's step %d and the rules' step %d differ" % (who, hist[2], t))
+    else:
+        hist = (None, 0, t, 0) + ((-1,) if own_eos else ()) if (rules is not None or row == "global") else ()
+    ws, stride = _row_workspace(rows, V, dev) if row == "global" and not in_place else (None, 0)
+    return head_entry(head, row, ban is not None, rules is not None), ((_ptr(ws), stride) if row == "global" else ()) + hist + rule, ws
 
 
 def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, want_dist=True, ban=None, row="auto", rules=None):
@@ -2164,22 +2175,8 @@ def pointer_head_decode(logits, mix_logits, source_map, copies, want_gen=True, w
     gen = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_gen else None
     dist = torch.empty(B, V, dtype=torch.float32, device=logits.device) if want_dist else None
     ids = torch.empty(B, dtype=torch.int64, device=logits.device)
-    head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S)
-    if rules is not None:
-        t, rule = _rule_operands(rules, B, "pointer_head_decode")
-        hist = _ban_operands_rules(ban, t, B, "pointer_head_decode")
-        if row == "global":
-            ws, stride = _row_workspace(B, V, logits.device)
-            A.call("case_pointer_head_decode_wide_rules", *head, _ptr(ws), stride, *hist, *rule, _stream())
-        else:
-            A.call("case_pointer_head_decode_rules", *head, *hist, *rule, _stream())
-    elif row == "global":
-        ws, stride = _row_workspace(B, V, logits.device)
-        A.call("case_pointer_head_decode_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, B, "pointer_head_decode"), _stream())
-    elif ban is None:
-        A.call("case_pointer_head_decode", *head, _stream())
-    else:
-        A.call("case_pointer_head_decode_ban", *head, *_ban_operands(ban, B, "pointer_head_decode"), _stream())
+    entry, tail, ws = _head_tail("decode", row, ban, rules, B, V, logits.device, "pointer_head_decode")
+    A.call(entry, _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(ids), None, B, V, S, *tail, _stream())
     return gen, dist, ids
 
 
@@ -2200,22 +2197,9 @@ def pointer_head_topk(logits, mix_logits, source_map, copies, width, want_gen=Fa
     dist = torch.empty(R, V, dtype=torch.float32, device=logits.device) if want_dist else None
     cand_p = torch.empty(R, width, dtype=torch.float32, device=logits.device)
     cand_id = torch.empty(R, width, dtype=torch.int64, device=logits.device)
-    head = (_ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, S, width)
-    if rules is not None:
-        t, rule = _rule_operands(rules, R, "pointer_head_topk")
-        hist = _ban_operands_rules(ban, t, R, "pointer_head_topk")
-        if row == "global":
-            ws, stride = _row_workspace(R, V, logits.device)
-            A.call("case_pointer_head_beam_wide_rules", *head, _ptr(ws), stride, *hist, *rule, _stream())
-        else:
-            A.call("case_pointer_head_beam_rules", *head, *hist, *rule, _stream())
-    elif row == "global":
-        ws, stride = _row_workspace(R, V, logits.device)
-        A.call("case_pointer_head_beam_wide", *head, _ptr(ws), stride, *_ban_operands_wide(ban, R, "pointer_head_topk"), _stream())
-    elif ban is None:
-        A.call("case_pointer_head_beam", *head, _stream())
-    else:
-        A.call("case_pointer_head_beam_ban", *head, *_ban_operands(ban, R, "pointer_head_topk"), _stream())
+    entry, tail, ws = _head_tail("beam", row, ban, rules, R, V, logits.device, "pointer_head_topk")
+    A.call(entry, _ptr(logits), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, _ptr(gen), _ptr(dist), _ptr(cand_p), _ptr(cand_id), R, V, S, width,
+           *tail, _stream())
     return gen, dist, cand_p, cand_id
 
 
@@ -2264,28 +2248,13 @@ def pointer_head_sample(logits, mix_logits, source_map, copies, ended, t_first, 
     tail = (_ptr(gen), _ptr(dist), _ptr(ids), _ptr(prob), _ptr(ended), _ptr(uniforms), R, V)
     draw = (float(temperature), min(int(top_k), 2 ** 31 - 1), float(top_p), int(seed), int(offset), state, int(eos), int(unk), int(pad),
             int(bool(t_first)), int(bool(t_last)))
-    if rules is not None:
-        t, rule = _rule_operands(rules, R, "pointer_head_sample")
-        hist = _ban_operands_rules(None if ban is None else tuple(ban) + (None,), t, R, "pointer_head_sample")[:4]
-        if row == "global":
-            ws, stride = _row_workspace(R, V, dev)
-            entry, draw = "case_pointer_head_sample_wide_rules", draw + (_ptr(ws), stride) + hist + rule + (_stream(),)
-        else:
-            entry, draw = "case_pointer_head_sample_rules", draw + hist + rule + (_stream(),)
-    elif row == "global":
-        in_place = logits is None and ban is None and V % 4 == 0 and src.data_ptr() % 16 == 0
-        ws, stride = (None, 0) if in_place else _row_workspace(R, V, dev)
-        hist = (None, 0, 0, 0) if ban is None else _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4]
-        entry, draw = "case_pointer_head_sample_wide", draw + (_ptr(ws), stride) + hist + (_stream(),)
-    elif ban is None:
-        entry, draw = "case_pointer_head_sample", draw + (_stream(),)
-    else:
-        entry, draw = "case_pointer_head_sample_ban", draw + _ban_operands(tuple(ban) + (None,), R, "pointer_head_sample")[:4] + (_stream(),)
+    in_place = rules is None and logits is None and ban is None and V % 4 == 0 and src.data_ptr() % 16 == 0  # (the wide form alone asks)
+    entry, hist, ws = _head_tail("sample", row, ban, rules, R, V, dev, "pointer_head_sample", own_eos=False, in_place=in_place)
     if logits is None:
-        A.call(entry, None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw)
+        A.call(entry, None, None, None, None, None, 0, _ptr(src), *tail, 0, *draw, *hist, _stream())
     else:
         src, mix_logits, cs, ptrs, lens, n, S = _head_operands(src, mix_logits, source_map, copies)
-        A.call(entry, _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, None, *tail, S, *draw)
+        A.call(entry, _ptr(src), _ptr(mix_logits), _ptr(source_map.keys), ptrs, lens, n, None, *tail, S, *draw, *hist, _stream())
     return gen, dist, ids, prob
 
 
@@ -2589,9 +2558,6 @@ def sequence_risk(token_probs, scored, cost, valid=None, alpha=5e-3, want_q=Fals
 
 
 # K32: the n-gram ban.  The fused heads apply it behind their row build (``ban=`` above); ``ngram_ban_`` is the same rule as a launch of its own.
-NGRAM_MAX_T = 256  # a history is staged in LDS (beside the vocabulary row in the LDS heads)
-
-
 def ngram_ban_supported():
     return bool(A.lib.case_abi_features() & A.FEAT_NGRAM_BAN)
 
@@ -2686,12 +2652,8 @@ def beam_advance(state, cand_p, cand_id, t, eos, length_penalty=1.0):
     args = (_ptr(cand_p), _ptr(cand_id), _ptr(state.alive), _ptr(state.cum), _ptr(state.len), _ptr(state.parent), _ptr(state.token),
             _ptr(state.hist_parent), _ptr(state.hist_token), _ptr(state.fin_key), _ptr(state.fin_step), _ptr(state.fin_slot), t, state.T, B, W,
             -1 if eos is None else eos)
-    if state.flat is None:
-        A.call("case_beam_advance", *args, _stream())
-    elif alpha != 1.0:
-        A.call("case_beam_advance_rules", *args, _ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T, alpha, _stream())
-    else:
-        A.call("case_beam_advance_ban", *args, _ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T, _stream())
+    flat = () if state.flat is None else (_ptr(state.flat[t % 2]), _ptr(state.flat[(t + 1) % 2]), state.T) + ((alpha,) if alpha != 1.0 else ())
+    A.call("case_beam_advance" + ("" if state.flat is None else "_rules" if alpha != 1.0 else "_ban"), *args, *flat, _stream())
 
 
 def beam_gather(src, dst, parent, t, valid_src=None, valid_dst=None):
@@ -2893,7 +2855,7 @@ def consensus_pick(f, weights, valid, candidates):
 
 
 # K34 / K35: n-gram counts and BLEU on token ids
-NGRAM_MAX_T, NGRAM_MAX_ORDER = 256, 4
+NGRAM_MAX_ORDER = 4  # (rows of up to NGRAM_MAX_T positions, as K32's histories)
 BLEU_SMOOTHINGS = {"none": 0, "add1": 1}
 
 
