@@ -9,61 +9,46 @@
 
 #include "case_hip.h"
 #include "common.h"
+#include "id_rows.h"
 
-constexpr int LCS_MAX_TA = 256;    // 4 words of 64 hypothesis positions
-constexpr int LCS_WAVES = 4;       // hypotheses per workgroup
 constexpr int CONSENSUS_MAX_N = 64;
 
 // ---- K30 -------------------------------------------------------------------------------------------------------------------------
-// One wave per hypothesis (b, n).  Lane l holds a[l + 64 j] for word j (the sentinel -1 from a_len on: a valid id is >= 0 and never equals
-// it), so one __ballot of "my token == t" is the 64-bit match mask M_j of the reference token t.  With V all ones at the start, every
-// reference token takes  V = (V + (V & M)) | (V & ~M)  (the addition carries from word j to word j + 1); the LCS length is the number of
-// zero bits of V.  A sentinel bit has M = 0, so V & ~M sets it again whatever the carry did to it: no length mask.  V, M and the carry are
-// wave-uniform 64-bit integers.  The reference row is read 64 tokens per load (one per lane) and handed round by readlane.
+// One wave per hypothesis (b, n), held as id_rows.h states (id_hold), so one __ballot of "my token == t" is the 64-bit match mask M_j of the
+// reference token t.  With V all ones at the start, every reference token takes  V = (V + (V & M)) | (V & ~M)  (the addition carries from
+// word j to word j + 1); the LCS length is the number of zero bits of V.  A sentinel bit has M = 0, so V & ~M sets it again whatever the
+// carry did to it: no length mask.  V, M and the carry are wave-uniform 64-bit integers.  The reference row is streamed (id_stream).
 template <int WORDS>
-__global__ __launch_bounds__(64 * LCS_WAVES) void lcs_pairs_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
+__global__ __launch_bounds__(64 * ID_WAVES) void lcs_pairs_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
                                                                   const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
                                                                   int32_t* __restrict__ lcs, float* __restrict__ f, const int64_t BN, const int N,
                                                                   const int M, const int Ta, const int Tb) {
   const int lane = threadIdx.x & 63;
-  const int64_t h = (int64_t)blockIdx.x * LCS_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: lengths, V and the loops stay scalar)
-  if (h >= BN) return;  // (whole waves: no barrier follows)
+  const int64_t h = id_wave_row();
+  if (h >= BN) return;
   const int64_t item = h / N;
-  int la = a_len[h];
-  la = la < 0 ? 0 : la > Ta ? Ta : la;
+  const int la = id_clamp(a_len[h], Ta);
   int32_t tok[WORDS];
-#pragma unroll
-  for (int j = 0; j < WORDS; ++j) {
-    const int pos = lane + 64 * j;
-    tok[j] = pos < la ? (int32_t)a[h * Ta + pos] : -1;
-  }
+  id_hold<WORDS>(a + h * Ta, 0, la, lane, tok);
   for (int m = 0; m < M; ++m) {
     const int64_t r = item * M + m;
-    int lb = b_len[r];
-    lb = lb < 0 ? 0 : lb > Tb ? Tb : lb;
-    const int64_t* __restrict__ row = b + r * Tb;
+    const int lb = id_clamp(b_len[r], Tb);
     unsigned long long V[WORDS];
 #pragma unroll
     for (int j = 0; j < WORDS; ++j) V[j] = ~0ull;
-    if (la > 0) {
-      for (int t0 = 0; t0 < lb; t0 += 64) {
-        const int mine = t0 + lane < lb ? (int32_t)row[t0 + lane] : -1;
-        const int n = lb - t0 < 64 ? lb - t0 : 64;
-        for (int i = 0; i < n; ++i) {
-          const int t = __builtin_amdgcn_readlane(mine, i);
-          unsigned long long carry = 0;
+    if (la > 0)
+      id_stream(b + r * Tb, lb, lane, [&](const int t, int) {
+        unsigned long long carry = 0;
 #pragma unroll
-          for (int j = 0; j < WORDS; ++j) {
-            const unsigned long long Mj = __ballot(tok[j] == t);
-            const unsigned long long Vj = V[j];
-            const unsigned long long s1 = Vj + (Vj & Mj);
-            const unsigned long long s2 = s1 + carry;
-            carry = (s1 < Vj || s2 < s1) ? 1ull : 0ull;
-            V[j] = s2 | (Vj & ~Mj);
-          }
+        for (int j = 0; j < WORDS; ++j) {
+          const unsigned long long Mj = __ballot(tok[j] == t);
+          const unsigned long long Vj = V[j];
+          const unsigned long long s1 = Vj + (Vj & Mj);
+          const unsigned long long s2 = s1 + carry;
+          carry = (s1 < Vj || s2 < s1) ? 1ull : 0ull;
+          V[j] = s2 | (Vj & ~Mj);
         }
-      }
-    }
+      });
     int len = 0;
 #pragma unroll
     for (int j = 0; j < WORDS; ++j) len += __popcll(~V[j]);
@@ -124,19 +109,14 @@ __global__ __launch_bounds__(64) void consensus_pick_kernel(const float* __restr
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
 extern "C" int case_lcs_pairs(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* lcs, float* f, int64_t B,
                               int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream) {
-  CASE_REQUIRE(a && a_len && b && b_len && lcs && f && B > 0 && N > 0 && M > 0 && Ta > 0 && Tb > 0 && B < (1ll << 31) && N < (1ll << 24) &&
-                   M < (1ll << 24) && B * N < (1ll << 31) && Tb < (1ll << 30),
-               "case_lcs_pairs: bad argument");
-  if (Ta > LCS_MAX_TA)
-    return case_set_error(CASE_E_UNSUPPORTED, "case_lcs_pairs: hypotheses of up to %d positions (got %lld)", LCS_MAX_TA, (long long)Ta);
+  CASE_REQUIRE(a && a_len && b && b_len && lcs && f && id_pairs_in_range(B, N, M, Ta, Tb), "case_lcs_pairs: bad argument");
+  if (Ta > ID_MAX_T)
+    return case_set_error(CASE_E_UNSUPPORTED, "case_lcs_pairs: hypotheses of up to %d positions (got %lld)", ID_MAX_T, (long long)Ta);
   const int64_t BN = B * N;
-  const dim3 grid((unsigned)((BN + LCS_WAVES - 1) / LCS_WAVES)), block(64 * LCS_WAVES);
-  if (Ta <= 64)
-    hipLaunchKernelGGL(lcs_pairs_kernel<1>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, lcs, f, BN, (int)N, (int)M, (int)Ta, (int)Tb);
-  else if (Ta <= 128)
-    hipLaunchKernelGGL(lcs_pairs_kernel<2>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, lcs, f, BN, (int)N, (int)M, (int)Ta, (int)Tb);
-  else
-    hipLaunchKernelGGL(lcs_pairs_kernel<4>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, lcs, f, BN, (int)N, (int)M, (int)Ta, (int)Tb);
+  id_dispatch_words(BN, Ta, [&](auto words, const dim3 grid, const dim3 block) {
+    hipLaunchKernelGGL(lcs_pairs_kernel<decltype(words)::value>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, lcs, f, BN, (int)N,
+                       (int)M, (int)Ta, (int)Tb);
+  });
   return case_check_launch("case_lcs_pairs");
 }
 

@@ -9,16 +9,14 @@
 
 #include "case_hip.h"
 #include "common.h"
-
-constexpr int METEOR_MAX_TA = 256;  // 4 words of 64 hypothesis positions
-constexpr int METEOR_WAVES = 4;     // hypotheses per workgroup
+#include "id_rows.h"
 
 // ---- K40 -------------------------------------------------------------------------------------------------------------------------
-// One wave per hypothesis (b, n), held as K30 / K34 hold it: lane l has a[l + 64 j] for word j, the sentinel -1 from a_len on.
+// One wave per hypothesis (b, n), held as id_rows.h states (id_hold).
 // The rule (evaluation/meteor.py) walks the hypothesis from its last position to its first and gives each position the LAST still-unmatched
 // reference position that holds the same id.  Read per id, that pairs the k-th-from-last occurrence in the hypothesis with the k-th-from-last
 // occurrence in the reference, so the transposed walk gives the same matches with wave-uniform state only: the reference is streamed
-// BACKWARDS (64 tokens per load, one per lane, handed round by readlane); for the token t at position p,
+// BACKWARDS (id_stream_back); for the token t at position p,
 //     M_j = __ballot(tok_j == t) & ~matched_j
 // marks the unmatched hypothesis positions that hold t, the HIGHEST set bit over the words is p's partner, its bit goes into `matched` and
 // its lane keeps p in `ref`.  The class stage is a second backward pass over what the first left: p was consumed by the exact stage exactly
@@ -55,36 +53,31 @@ __device__ __forceinline__ void meteor_take(const int32_t (&key)[WORDS], const i
 }
 
 template <int WORDS, bool CLASSES>
-__global__ __launch_bounds__(64 * METEOR_WAVES) void meteor_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
-                                                                   const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
-                                                                   const int32_t* __restrict__ classes, const int V, const double alpha,
-                                                                   const double beta, const double gamma, int32_t* __restrict__ counts,
-                                                                   float* __restrict__ pair, double* __restrict__ best_out,
-                                                                   int32_t* __restrict__ best_ref_out, int32_t* __restrict__ align, const int64_t BN,
-                                                                   const int N, const int M, const int Ta, const int Tb) {
+__global__ __launch_bounds__(64 * ID_WAVES) void meteor_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
+                                                               const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
+                                                               const int32_t* __restrict__ classes, const int V, const double alpha,
+                                                               const double beta, const double gamma, int32_t* __restrict__ counts,
+                                                               float* __restrict__ pair, double* __restrict__ best_out,
+                                                               int32_t* __restrict__ best_ref_out, int32_t* __restrict__ align, const int64_t BN,
+                                                               const int N, const int M, const int Ta, const int Tb) {
   const int lane = threadIdx.x & 63;
-  const int64_t h = (int64_t)blockIdx.x * METEOR_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: the masks and the loops stay scalar)
-  if (h >= BN) return;  // (whole waves: no barrier follows)
+  const int64_t h = id_wave_row();
+  if (h >= BN) return;
   const int64_t item = h / N;
-  int la = a_len[h];
-  la = la < 0 ? 0 : la > Ta ? Ta : la;
+  const int la = id_clamp(a_len[h], Ta);
   int32_t tok[WORDS], cls[WORDS];
+  id_hold<WORDS>(a + h * Ta, 0, la, lane, tok);
+  const auto class_of = [&](const int id) { return CLASSES && id >= 0 && id < V ? classes[id] : -1; };  // (an id without a class: negative)
 #pragma unroll
   for (int j = 0; j < WORDS; ++j) {
-    const int pos = lane + 64 * j;
-    tok[j] = pos < la ? (int32_t)a[h * Ta + pos] : -1;
-    cls[j] = -1;
-    if (CLASSES && tok[j] >= 0 && tok[j] < V) {
-      const int c = classes[tok[j]];
-      cls[j] = c < 0 ? -1 : c;
-    }
+    const int c = class_of(tok[j]);
+    cls[j] = c < 0 ? -1 : c;
   }
   double best = 0.0;
   int best_ref = -1;
   for (int m = 0; m < M; ++m) {
     const int64_t r = item * M + m;
-    int lb = b_len[r];
-    lb = lb < 0 ? 0 : lb > Tb ? Tb : lb;
+    const int lb = id_clamp(b_len[r], Tb);
     const int64_t* __restrict__ row = b + r * Tb;
     unsigned long long matched[WORDS];
     int32_t ref[WORDS];
@@ -95,34 +88,21 @@ __global__ __launch_bounds__(64 * METEOR_WAVES) void meteor_kernel(const int64_t
     }
     int exact = 0, total = 0, chunks = 0;
     if (la > 0 && lb > 0) {
-      // the exact stage: the aligned 64-token loads from the last (a partial one) down to the first
-      for (int t0 = (lb - 1) & ~63; t0 >= 0; t0 -= 64) {
-        const int mine = t0 + lane < lb ? (int32_t)row[t0 + lane] : -1;
-        const int n = lb - t0 < 64 ? lb - t0 : 64;
-        for (int i = n - 1; i >= 0; --i) {
-          const int t = __builtin_amdgcn_readlane(mine, i);
-          if (t >= 0) meteor_take<WORDS>(tok, t, t0 + i, lane, matched, ref);  // (a negative id is no token: it must not meet the sentinel)
-        }
-      }
+      // the exact stage
+      id_stream_back(row, lb, lane, [](const int id) { return id; }, [&](const int t, const int p) {
+        if (t >= 0) meteor_take<WORDS>(tok, t, p, lane, matched, ref);  // (a negative id is no token: it must not meet the sentinel)
+      });
 #pragma unroll
       for (int j = 0; j < WORDS; ++j) exact += __popcll(matched[j]);
       total = exact;
       if (CLASSES) {
-        for (int t0 = (lb - 1) & ~63; t0 >= 0; t0 -= 64) {
-          const int id = t0 + lane < lb ? (int32_t)row[t0 + lane] : -1;
-          int mine = -1;
-          if (id >= 0 && id < V) mine = classes[id];
-          const int n = lb - t0 < 64 ? lb - t0 : 64;
-          for (int i = n - 1; i >= 0; --i) {
-            const int c = __builtin_amdgcn_readlane(mine, i);
-            if (c < 0) continue;  // (uniform)
-            const int p = t0 + i;
-            unsigned long long taken = 0ull;
+        id_stream_back(row, lb, lane, class_of, [&](const int c, const int p) {
+          if (c < 0) return;  // (uniform)
+          unsigned long long taken = 0ull;
 #pragma unroll
-            for (int j = 0; j < WORDS; ++j) taken |= __ballot(ref[j] == p);
-            if (taken == 0ull) meteor_take<WORDS>(cls, c, p, lane, matched, ref);
-          }
-        }
+          for (int j = 0; j < WORDS; ++j) taken |= __ballot(ref[j] == p);
+          if (taken == 0ull) meteor_take<WORDS>(cls, c, p, lane, matched, ref);
+        });
         total = 0;
 #pragma unroll
         for (int j = 0; j < WORDS; ++j) total += __popcll(matched[j]);
@@ -162,39 +142,27 @@ __global__ __launch_bounds__(64 * METEOR_WAVES) void meteor_kernel(const int64_t
 }
 
 // ---- C ABI -----------------------------------------------------------------------------------------------------------------------
-template <int WORDS>
-static void meteor_launch(const dim3 grid, const dim3 block, hipStream_t stream, const int64_t* a, const int32_t* a_len, const int64_t* b,
-                          const int32_t* b_len, const int32_t* classes, int V, double alpha, double beta, double gamma, int32_t* counts, float* pair,
-                          double* best, int32_t* best_ref, int32_t* align, int64_t BN, int N, int M, int Ta, int Tb) {
-  if (classes)
-    hipLaunchKernelGGL((meteor_kernel<WORDS, true>), grid, block, 0, stream, a, a_len, b, b_len, classes, V, alpha, beta, gamma, counts, pair, best,
-                       best_ref, align, BN, N, M, Ta, Tb);
-  else
-    hipLaunchKernelGGL((meteor_kernel<WORDS, false>), grid, block, 0, stream, a, a_len, b, b_len, classes, V, alpha, beta, gamma, counts, pair, best,
-                       best_ref, align, BN, N, M, Ta, Tb);
-}
-
 extern "C" int case_meteor(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, const int32_t* classes, int64_t V,
                            double alpha, double beta, double gamma, int32_t* counts, float* meteor_pair, double* meteor, int32_t* best_ref,
                            int32_t* align, int64_t B, int64_t N, int64_t M, int64_t Ta, int64_t Tb, case_stream_t stream) {
-  CASE_REQUIRE(a && a_len && b && b_len && counts && meteor_pair && meteor && best_ref && B > 0 && N > 0 && M > 0 && Ta > 0 && Tb > 0 &&
-                   B < (1ll << 31) && N < (1ll << 24) && M < (1ll << 24) && B * N < (1ll << 31) && Tb < (1ll << 30),
+  CASE_REQUIRE(a && a_len && b && b_len && counts && meteor_pair && meteor && best_ref && id_pairs_in_range(B, N, M, Ta, Tb),
                "case_meteor: bad argument");
   CASE_REQUIRE(classes ? (V > 0 && V < (1ll << 31)) : V == 0, "case_meteor: a class table of V = %lld entries (0 without a table)", (long long)V);
   CASE_REQUIRE(alpha >= 0.0 && alpha <= 1.0 && gamma >= 0.0 && gamma <= 1.0 && beta >= 0.0 && isfinite(beta),
                "case_meteor: alpha and gamma in [0, 1], beta >= 0 and finite (got %g, %g, %g)", alpha, beta, gamma);
-  if (Ta > METEOR_MAX_TA)
-    return case_set_error(CASE_E_UNSUPPORTED, "case_meteor: hypotheses of up to %d positions (got %lld)", METEOR_MAX_TA, (long long)Ta);
+  if (Ta > ID_MAX_T)
+    return case_set_error(CASE_E_UNSUPPORTED, "case_meteor: hypotheses of up to %d positions (got %lld)", ID_MAX_T, (long long)Ta);
   const int64_t BN = B * N;
-  const dim3 grid((unsigned)((BN + METEOR_WAVES - 1) / METEOR_WAVES)), block(64 * METEOR_WAVES);
-  if (Ta <= 64)
-    meteor_launch<1>(grid, block, (hipStream_t)stream, a, a_len, b, b_len, classes, (int)V, alpha, beta, gamma, counts, meteor_pair, meteor, best_ref,
-                     align, BN, (int)N, (int)M, (int)Ta, (int)Tb);
-  else if (Ta <= 128)
-    meteor_launch<2>(grid, block, (hipStream_t)stream, a, a_len, b, b_len, classes, (int)V, alpha, beta, gamma, counts, meteor_pair, meteor, best_ref,
-                     align, BN, (int)N, (int)M, (int)Ta, (int)Tb);
-  else
-    meteor_launch<4>(grid, block, (hipStream_t)stream, a, a_len, b, b_len, classes, (int)V, alpha, beta, gamma, counts, meteor_pair, meteor, best_ref,
-                     align, BN, (int)N, (int)M, (int)Ta, (int)Tb);
+  id_dispatch_words(BN, Ta, [&](auto words, const dim3 grid, const dim3 block) {
+    const auto launch = [&](auto with_classes) {
+      hipLaunchKernelGGL((meteor_kernel<decltype(words)::value, decltype(with_classes)::value>), grid, block, 0, (hipStream_t)stream, a, a_len, b,
+                         b_len, classes, (int)V, alpha, beta, gamma, counts, meteor_pair, meteor, best_ref, align, BN, (int)N, (int)M, (int)Ta,
+                         (int)Tb);
+    };
+    if (classes)
+      launch(std::true_type());
+    else
+      launch(std::false_type());
+  });
   return case_check_launch("case_meteor");
 }

@@ -12,14 +12,13 @@
 
 #include "case_hip.h"
 #include "common.h"
+#include "id_rows.h"
 
-constexpr int NGRAM_MAX_TA = 256;  // 4 words of 64 hypothesis positions
-constexpr int NGRAM_WAVES = 4;     // hypotheses per workgroup
 constexpr int NGRAM_ORDERS = 4;
 
 // ---- K34 -------------------------------------------------------------------------------------------------------------------------
-// One wave per hypothesis (b, n), held as K30 holds it: lane l has a[l + 64 j] for word j, the sentinel -1 from a_len on.  For a token t at
-// position p of some sequence s,  M(p) = __ballot(tok == t)  marks the hypothesis positions that hold t, and
+// One wave per hypothesis (b, n), held as id_rows.h states (id_hold).  For a token t at position p of some sequence s,
+// M(p) = __ballot(tok == t)  marks the hypothesis positions that hold t, and
 //     D_1(p) = M(p),   D_k(p) = M(p) & (D_{k-1}(p - 1) << 1)        (the shift carries bit 63 of word j into bit 0 of word j + 1)
 // has bit i set exactly when the k-gram of the hypothesis that ENDS at i equals the k-gram of s that ends at p.  The D_k are wave-uniform and
 // live from one token to the next (and from one 64-token load of s to the next); lane i adds its own bit of D_k(p) to a counter, which
@@ -91,24 +90,19 @@ __device__ __forceinline__ void ngram_store(int32_t* __restrict__ out, const int
 }
 
 template <int WORDS>
-__global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_counts_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
-                                                                       const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
-                                                                       int32_t* __restrict__ clip, int32_t* __restrict__ clip_any,
-                                                                       int32_t* __restrict__ hit, int32_t* __restrict__ hit_any,
-                                                                       int32_t* __restrict__ distinct, const int64_t BN, const int N, const int M,
-                                                                       const int Ta, const int Tb, const int max_n) {
+__global__ __launch_bounds__(64 * ID_WAVES) void ngram_counts_kernel(const int64_t* __restrict__ a, const int32_t* __restrict__ a_len,
+                                                                    const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
+                                                                    int32_t* __restrict__ clip, int32_t* __restrict__ clip_any,
+                                                                    int32_t* __restrict__ hit, int32_t* __restrict__ hit_any,
+                                                                    int32_t* __restrict__ distinct, const int64_t BN, const int N, const int M,
+                                                                    const int Ta, const int Tb, const int max_n) {
   const int lane = threadIdx.x & 63;
-  const int64_t h = (int64_t)blockIdx.x * NGRAM_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform: the masks and the loops stay scalar)
-  if (h >= BN) return;  // (whole waves: no barrier follows)
+  const int64_t h = id_wave_row();
+  if (h >= BN) return;
   const int64_t item = h / N;
-  int la = a_len[h];
-  la = la < 0 ? 0 : la > Ta ? Ta : la;
+  const int la = id_clamp(a_len[h], Ta);
   int32_t tok[WORDS];
-#pragma unroll
-  for (int j = 0; j < WORDS; ++j) {
-    const int pos = lane + 64 * j;
-    tok[j] = pos < la ? (int32_t)a[h * Ta + pos] : -1;
-  }
+  id_hold<WORDS>(a + h * Ta, 0, la, lane, tok);
   NgramMasks prev[WORDS];
   int c_hyp[NGRAM_ORDERS][WORDS], c_ref[NGRAM_ORDERS][WORDS], c_max[NGRAM_ORDERS][WORDS], earlier[NGRAM_ORDERS][WORDS];
 #pragma unroll
@@ -119,19 +113,13 @@ __global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_counts_kernel(const in
     for (int k = 0; k < NGRAM_ORDERS; ++k) c_hyp[k][j] = c_max[k][j] = earlier[k][j] = 0;
   }
   // the hypothesis against itself
-#pragma unroll
-  for (int w = 0; w < WORDS; ++w) {
-    const int n = la - 64 * w < 64 ? la - 64 * w : 64;
-    for (int i = 0; i < n; ++i) {
-      const int t = __builtin_amdgcn_readlane(tok[w], i);
-      const int p = 64 * w + i;
-      ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) {
-        const int bit = ngram_own_bit(d);
-        c_hyp[k][j] += bit;
-        earlier[k][j] |= p < lane + 64 * j ? bit : 0;
-      });
-    }
-  }
+  id_stream_held<WORDS>(tok, la, [&](const int t, const int p) {
+    ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) {
+      const int bit = ngram_own_bit(d);
+      c_hyp[k][j] += bit;
+      earlier[k][j] |= p < lane + 64 * j ? bit : 0;
+    });
+  });
   int total[NGRAM_ORDERS];
 #pragma unroll
   for (int k = 0; k < NGRAM_ORDERS; ++k) {
@@ -147,9 +135,7 @@ __global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_counts_kernel(const in
   int got_clip[NGRAM_ORDERS], got_hit[NGRAM_ORDERS];
   for (int m = 0; m < M; ++m) {
     const int64_t r = item * M + m;
-    int lb = b_len[r];
-    lb = lb < 0 ? 0 : lb > Tb ? Tb : lb;
-    const int64_t* __restrict__ row = b + r * Tb;
+    const int lb = id_clamp(b_len[r], Tb);
 #pragma unroll
     for (int j = 0; j < WORDS; ++j) {
 #pragma unroll
@@ -157,16 +143,10 @@ __global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_counts_kernel(const in
 #pragma unroll
       for (int k = 0; k < NGRAM_ORDERS; ++k) c_ref[k][j] = 0;
     }
-    if (la > 0) {
-      for (int t0 = 0; t0 < lb; t0 += 64) {  // (prev carries D_k(p - 1) from one load to the next)
-        const int mine = t0 + lane < lb ? (int32_t)row[t0 + lane] : -1;
-        const int n = lb - t0 < 64 ? lb - t0 : 64;
-        for (int i = 0; i < n; ++i) {
-          const int t = __builtin_amdgcn_readlane(mine, i);
-          ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { c_ref[k][j] += ngram_own_bit(d); });
-        }
-      }
-    }
+    if (la > 0)
+      id_stream(b + r * Tb, lb, lane, [&](const int t, int) {  // (prev carries D_k(p - 1) from one position, and one load, to the next)
+        ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { c_ref[k][j] += ngram_own_bit(d); });
+      });
     ngram_totals<WORDS>(c_hyp, c_ref, got_clip, got_hit);
 #pragma unroll
     for (int k = 0; k < NGRAM_ORDERS; ++k)
@@ -240,8 +220,8 @@ __global__ __launch_bounds__(256) void bleu_scores_kernel(const int32_t* __restr
 
 // ---- K43 -------------------------------------------------------------------------------------------------------------------------
 // The distinct k-grams of a row of any length (ROUGE-N's |R|): K34's self-pass over a row that does not fit 64 WORDS positions.  One wave per
-// row.  A WINDOW of 64 WORDS positions starting at s is held as K34 holds a hypothesis (lane l, word j: position s + l + 64 j, the sentinel -1
-// from the row's length on), and the row is streamed from position 0 to the window's end through ngram_step: a set bit of D_k(p) with
+// row.  A WINDOW of 64 WORDS positions starting at s is held as id_rows.h states (id_hold with first = s), and the row is streamed from
+// position 0 to the window's end through ngram_step: a set bit of D_k(p) with
 // p below the bit's own position says "the k-gram that ends here ended at p already", and that position drops out (the masks are
 // wave-uniform, so D_k, the "behind p" masks and the dropped-out sets all live in scalar registers).  What is left is counted.
 // The seam: the D_k recurrence never sets a bit below k - 1 of a window, because that k-gram starts in the window before.  So consecutive
@@ -252,15 +232,14 @@ __global__ __launch_bounds__(256) void bleu_scores_kernel(const int32_t* __restr
 constexpr int NGRAM_SEAM = NGRAM_ORDERS - 1;
 
 template <int WORDS>
-__global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_distinct_kernel(const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
-                                                                         int32_t* __restrict__ distinct, const int64_t rows, const int Tb,
-                                                                         const int max_n) {
+__global__ __launch_bounds__(64 * ID_WAVES) void ngram_distinct_kernel(const int64_t* __restrict__ b, const int32_t* __restrict__ b_len,
+                                                                      int32_t* __restrict__ distinct, const int64_t rows, const int Tb,
+                                                                      const int max_n) {
   constexpr int STRIDE = 64 * WORDS - NGRAM_SEAM;
   const int lane = threadIdx.x & 63;
-  const int64_t r = (int64_t)blockIdx.x * NGRAM_WAVES + __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);  // (uniform, as in K34)
-  if (r >= rows) return;  // (whole waves: no barrier follows)
-  int len = b_len[r];
-  len = len < 0 ? 0 : len > Tb ? Tb : len;
+  const int64_t r = id_wave_row();
+  if (r >= rows) return;
+  const int len = id_clamp(b_len[r], Tb);
   const int64_t* __restrict__ row = b + r * Tb;
   int total[NGRAM_ORDERS];
 #pragma unroll
@@ -272,30 +251,24 @@ __global__ __launch_bounds__(64 * NGRAM_WAVES) void ngram_distinct_kernel(const 
     int32_t tok[WORDS];
     NgramMasks prev[WORDS];
     unsigned long long earlier[NGRAM_ORDERS][WORDS];  // (wave-uniform like the D_k: the whole self-pass stays in scalar registers)
+    id_hold<WORDS>(row, s, end, lane, tok);
 #pragma unroll
     for (int j = 0; j < WORDS; ++j) {
-      const int pos = s + lane + 64 * j;
-      tok[j] = pos < end ? (int32_t)row[pos] : -1;
 #pragma unroll
       for (int k = 0; k + 1 < NGRAM_ORDERS; ++k) prev[j].d[k] = 0ull;
 #pragma unroll
       for (int k = 0; k < NGRAM_ORDERS; ++k) earlier[k][j] = 0ull;
     }
-    for (int t0 = 0; t0 < end; t0 += 64) {  // (prev carries D_k(p - 1) from one load to the next)
-      const int mine = t0 + lane < end ? (int32_t)row[t0 + lane] : -1;
-      const int n = end - t0 < 64 ? end - t0 : 64;
-      for (int i = 0; i < n; ++i) {
-        const int t = __builtin_amdgcn_readlane(mine, i);
-        const int p = t0 + i - s;  // the stream's position seen from the window: negative before it
-        unsigned long long above[WORDS];  // the positions of word j that lie behind p
+    id_stream(row, end, lane, [&](const int t, const int at) {  // (prev carries D_k(p - 1) from one position, and one load, to the next)
+      const int p = at - s;  // the stream's position seen from the window: negative before it
+      unsigned long long above[WORDS];  // the positions of word j that lie behind p
 #pragma unroll
-        for (int j = 0; j < WORDS; ++j) {
-          const int q = p - 64 * j;
-          above[j] = q < 0 ? ~0ull : q >= 63 ? 0ull : ~0ull << (q + 1);
-        }
-        ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { earlier[k][j] |= d & above[j]; });
+      for (int j = 0; j < WORDS; ++j) {
+        const int q = p - 64 * j;
+        above[j] = q < 0 ? ~0ull : q >= 63 ? 0ull : ~0ull << (q + 1);
       }
-    }
+      ngram_step<WORDS>(tok, t, prev, [&](const int k, const int j, const unsigned long long d) { earlier[k][j] |= d & above[j]; });
+    });
 #pragma unroll
     for (int k = 0; k < NGRAM_ORDERS; ++k)
 #pragma unroll
@@ -360,22 +333,18 @@ extern "C" int case_ngram_distinct(const int64_t* b, const int32_t* b_len, int32
                                    case_stream_t stream) {
   CASE_REQUIRE(b && b_len && distinct && rows > 0 && Tb > 0 && rows < (1ll << 31) && Tb < (1ll << 30) && max_n >= 1 && max_n <= NGRAM_ORDERS,
                "case_ngram_distinct: bad argument");
-  const dim3 grid((unsigned)((rows + NGRAM_WAVES - 1) / NGRAM_WAVES)), block(64 * NGRAM_WAVES);
-  if (Tb <= 64)
-    hipLaunchKernelGGL(ngram_distinct_kernel<1>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
-  else if (Tb <= 128)
-    hipLaunchKernelGGL(ngram_distinct_kernel<2>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
-  else
-    hipLaunchKernelGGL(ngram_distinct_kernel<4>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb, (int)max_n);
+  id_dispatch_words(rows, Tb, [&](auto words, const dim3 grid, const dim3 block) {
+    hipLaunchKernelGGL(ngram_distinct_kernel<decltype(words)::value>, grid, block, 0, (hipStream_t)stream, b, b_len, distinct, rows, (int)Tb,
+                       (int)max_n);
+  });
   return case_check_launch("case_ngram_distinct");
 }
 
 extern "C" int case_rouge_n_scores(const int32_t* hit, const int32_t* hyp_distinct, const int32_t* ref_distinct, const int32_t* b_len,
                                    float* f_pair, double* f, double* p, double* r, int32_t* best_ref, int64_t B, int64_t N, int64_t M,
                                    int32_t max_n, case_stream_t stream) {
-  CASE_REQUIRE(hit && hyp_distinct && ref_distinct && b_len && f_pair && f && p && r && best_ref && B > 0 && N > 0 && M > 0 &&
-                   B < (1ll << 31) && N < (1ll << 24) && M < (1ll << 24) && B * N < (1ll << 31) && B * N * M < (1ll << 37) && max_n >= 1 &&
-                   max_n <= NGRAM_ORDERS,
+  CASE_REQUIRE(hit && hyp_distinct && ref_distinct && b_len && f_pair && f && p && r && best_ref && id_pairs_in_range(B, N, M) &&
+                   B * N * M < (1ll << 37) && max_n >= 1 && max_n <= NGRAM_ORDERS,
                "case_rouge_n_scores: bad argument");
   const int64_t total = B * N * NGRAM_ORDERS;
   hipLaunchKernelGGL(rouge_n_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, hit, hyp_distinct,
@@ -386,32 +355,24 @@ extern "C" int case_rouge_n_scores(const int32_t* hit, const int32_t* hyp_distin
 extern "C" int case_ngram_counts(const int64_t* a, const int32_t* a_len, const int64_t* b, const int32_t* b_len, int32_t* clip, int32_t* clip_any,
                                  int32_t* hit, int32_t* hit_any, int32_t* distinct, int64_t B, int64_t N, int64_t M, int64_t Ta, int64_t Tb,
                                  int32_t max_n, case_stream_t stream) {
-  CASE_REQUIRE(a && a_len && b && b_len && clip && clip_any && hit && hit_any && distinct && B > 0 && N > 0 && M > 0 && Ta > 0 && Tb > 0 &&
-                   B < (1ll << 31) && N < (1ll << 24) && M < (1ll << 24) && B * N < (1ll << 31) && Tb < (1ll << 30) && max_n >= 1 &&
+  CASE_REQUIRE(a && a_len && b && b_len && clip && clip_any && hit && hit_any && distinct && id_pairs_in_range(B, N, M, Ta, Tb) && max_n >= 1 &&
                    max_n <= NGRAM_ORDERS,
                "case_ngram_counts: bad argument");
-  if (Ta > NGRAM_MAX_TA)
-    return case_set_error(CASE_E_UNSUPPORTED, "case_ngram_counts: hypotheses of up to %d positions (got %lld)", NGRAM_MAX_TA, (long long)Ta);
+  if (Ta > ID_MAX_T)
+    return case_set_error(CASE_E_UNSUPPORTED, "case_ngram_counts: hypotheses of up to %d positions (got %lld)", ID_MAX_T, (long long)Ta);
   const int64_t BN = B * N;
-  const dim3 grid((unsigned)((BN + NGRAM_WAVES - 1) / NGRAM_WAVES)), block(64 * NGRAM_WAVES);
-  if (Ta <= 64)
-    hipLaunchKernelGGL(ngram_counts_kernel<1>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
-                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
-  else if (Ta <= 128)
-    hipLaunchKernelGGL(ngram_counts_kernel<2>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
-                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
-  else
-    hipLaunchKernelGGL(ngram_counts_kernel<4>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit, hit_any, distinct, BN,
-                       (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
+  id_dispatch_words(BN, Ta, [&](auto words, const dim3 grid, const dim3 block) {
+    hipLaunchKernelGGL(ngram_counts_kernel<decltype(words)::value>, grid, block, 0, (hipStream_t)stream, a, a_len, b, b_len, clip, clip_any, hit,
+                       hit_any, distinct, BN, (int)N, (int)M, (int)Ta, (int)Tb, (int)max_n);
+  });
   return case_check_launch("case_ngram_counts");
 }
 
 extern "C" int case_bleu_scores(const int32_t* clip, const int32_t* clip_any, const int32_t* a_len, const int32_t* b_len, float* bleu_pair,
                                 double* bleu_any, double* bp, int64_t B, int64_t N, int64_t M, int32_t max_n, int32_t smoothing,
                                 case_stream_t stream) {
-  CASE_REQUIRE(clip && clip_any && a_len && b_len && bleu_pair && bleu_any && B > 0 && N > 0 && M > 0 && B < (1ll << 31) && N < (1ll << 24) &&
-                   M < (1ll << 24) && B * N < (1ll << 31) && B * N * (M + 1) < (1ll << 39) && max_n >= 1 && max_n <= NGRAM_ORDERS &&
-                   (smoothing == 0 || smoothing == 1),
+  CASE_REQUIRE(clip && clip_any && a_len && b_len && bleu_pair && bleu_any && id_pairs_in_range(B, N, M) && B * N * (M + 1) < (1ll << 39) &&
+                   max_n >= 1 && max_n <= NGRAM_ORDERS && (smoothing == 0 || smoothing == 1),
                "case_bleu_scores: bad argument");
   const int64_t total = B * N * (M + 1);
   hipLaunchKernelGGL(bleu_scores_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, clip, clip_any, a_len, b_len,

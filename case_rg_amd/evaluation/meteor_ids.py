@@ -9,7 +9,7 @@ truths is padded with all-PAD rows); an item without a present reference scores 
 (``bleu_ids``' deviation), and the stem / synonym stages are one caller-provided class table (``meteor.stem_classes`` builds one).  Limits:
 hypotheses of at most 256 positions, ids in [0, 2^31)."""
 from .. import ops
-from .rouge_ids import _compact, _pool
+from .rouge_ids import _id_rows
 
 
 def meteor_ids(hyp, ref, specials, classes=None, alpha=0.9, beta=3.0, gamma=0.5, remove_duplicates=False, want_align=False):
@@ -20,16 +20,7 @@ def meteor_ids(hyp, ref, specials, classes=None, alpha=0.9, beta=3.0, gamma=0.5,
     against all present references and ``best_ref`` the lowest index that reaches it (-1 without a present reference, where ``meteor`` is
     0).  An absent reference reads 0.  ``classes``: int32 [V] on the ids' device for the second stage (None: exact matches only).
     ``remove_duplicates``: the compacted HYPOTHESES go through ``remove_duplicate`` first (K33), as in ``rouge_l_ids``."""
-    bos, pad, eos, unk = specials
-    hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
-    if hyp.shape[0] != ref.shape[0]:
-        raise ValueError("meteor_ids: %d hypothesis items, %d reference items" % (hyp.shape[0], ref.shape[0]))
-    if hyp.shape[2] > ops.METEOR_MAX_T:
-        raise ValueError("meteor_ids: hypotheses of up to %d positions (got %d)" % (ops.METEOR_MAX_T, hyp.shape[2]))
-    a, a_len = _compact(hyp, bos, pad, eos, unk)
-    if remove_duplicates:
-        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
-    b, b_len = _compact(ref, bos, pad, eos)
+    a, a_len, b, b_len = _id_rows("meteor_ids", hyp, ref, specials, ops.METEOR_MAX_T, remove_duplicates)
     out = ops.meteor(a, a_len, b, b_len, classes, alpha, beta, gamma, want_align)
     counts = out.pop("counts")
     out.update(matches=counts[..., 0], exact=counts[..., 1], chunks=counts[..., 2], ref_valid=b_len.gt(0))

@@ -10,7 +10,7 @@ truths is padded with all-PAD rows).  Limits: hypotheses of at most 256 position
 import torch
 
 from .. import ops
-from .rouge_ids import _compact, _pool
+from .rouge_ids import _id_rows
 
 
 def _orders(length, max_n):
@@ -27,18 +27,9 @@ def bleu_ids(hyp, ref, specials, max_n=4, smoothing="none", remove_duplicates=Fa
     all present references (``bp``: its brevity penalty); ``clip`` / ``clip_any`` are the numerators of the modified precisions of the orders
     1..4 and ``total`` their denominators before max(1, .).  An absent reference reads 0; an item without a present one has ``bleu`` 0.
     ``remove_duplicates``: the compacted HYPOTHESES go through ``remove_duplicate`` first (K33), as in ``rouge_l_ids``."""
-    bos, pad, eos, unk = specials
-    hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
-    if hyp.shape[0] != ref.shape[0]:
-        raise ValueError("bleu_ids: %d hypothesis items, %d reference items" % (hyp.shape[0], ref.shape[0]))
-    if hyp.shape[2] > ops.NGRAM_MAX_T:
-        raise ValueError("bleu_ids: hypotheses of up to %d positions (got %d)" % (ops.NGRAM_MAX_T, hyp.shape[2]))
     if smoothing not in ops.BLEU_SMOOTHINGS:
         raise ValueError("bleu_ids: smoothing must be 'none' or 'add1', not %r" % (smoothing,))
-    a, a_len = _compact(hyp, bos, pad, eos, unk)
-    if remove_duplicates:
-        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
-    b, b_len = _compact(ref, bos, pad, eos)
+    a, a_len, b, b_len = _id_rows("bleu_ids", hyp, ref, specials, ops.NGRAM_MAX_T, remove_duplicates)
     counts = ops.ngram_counts(a, a_len, b, b_len, max_n)
     pair, bleu, bp = ops.bleu_scores(counts, a_len, b_len, max_n, smoothing)
     return dict(clip=counts["clip"], clip_any=counts["clip_any"], total=_orders(a_len, max_n), bleu_pair=pair, bleu=bleu, bp=bp,
@@ -59,14 +50,8 @@ def ngram_overlap_ids(hyp, source, specials, max_n=4):
     Every source row is compacted on its own and k-grams do not span rows.  With one flat row this is Eval_Overlap.py's ratio exactly; with
     the passages as rows [B, P, L] it leaves out the few n-grams that the reference, which concatenates the passages of an item first,
     counts across a passage boundary."""
-    bos, pad, eos, unk = specials
-    hyp, source = _pool(hyp, "hyp"), _pool(source, "source")
-    if hyp.shape[0] != source.shape[0]:
-        raise ValueError("ngram_overlap_ids: %d answer items, %d source items" % (hyp.shape[0], source.shape[0]))
-    if hyp.shape[2] > ops.NGRAM_MAX_T:
-        raise ValueError("ngram_overlap_ids: answers of up to %d positions (got %d)" % (ops.NGRAM_MAX_T, hyp.shape[2]))
-    a, a_len = _compact(hyp, bos, pad, eos, unk)
-    b, b_len = _compact(source, bos, pad, eos)
+    a, a_len, b, b_len = _id_rows("ngram_overlap_ids", hyp, source, specials, ops.NGRAM_MAX_T, held=("answer", "answers"),
+                                  streamed=("source", "source"))
     counts = ops.ngram_counts(a, a_len, b, b_len, max_n)
     distinct = counts["distinct"].double()
     return torch.where(distinct > 0, counts["hit_any"].double() / distinct.clamp_min(1), torch.zeros_like(distinct))

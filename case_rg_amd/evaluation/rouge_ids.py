@@ -24,10 +24,26 @@ def _compact(ids, bos, pad, eos, unk=None):
     return kept.view(B, N, T), count.view(B, N)
 
 
-def _pool(ids, what):
+def _pool(who, ids, what):
     if not torch.is_tensor(ids) or ids.dtype != torch.int64 or ids.dim() not in (2, 3):
-        raise TypeError("%s must be an int64 tensor [B, T] or [B, N, T]" % what)
+        raise TypeError("%s: %s must be an int64 tensor [B, T] or [B, N, T]" % (who, what))
     return ids.unsqueeze(1) if ids.dim() == 2 else ids
+
+
+def _id_rows(who, hyp, ref, specials, max_t, remove_duplicates=False, held=("hypothesis", "hypotheses"), streamed=("reference", "ref")):
+    """The operands of a metric on token ids from raw rows: hyp int64 [B, T] or [B, N, T] and ref int64 [B, T'] or [B, M, T'] of one batch, T <=
+    max_t -> (a, a_len, b, b_len), compacted; an empty hypothesis becomes [UNK], and with ``remove_duplicates`` the compacted hypotheses go
+    through ``remove_duplicate`` (K33).  ``held`` / ``streamed``: what the messages call the two sides (the latter with the argument's name)."""
+    bos, pad, eos, unk = specials
+    hyp, ref = _pool(who, hyp, "hyp"), _pool(who, ref, streamed[1])
+    if hyp.shape[0] != ref.shape[0]:
+        raise ValueError("%s: %d %s items, %d %s items" % (who, hyp.shape[0], held[0], ref.shape[0], streamed[0]))
+    if hyp.shape[2] > max_t:
+        raise ValueError("%s: %s of up to %d positions (got %d)" % (who, held[1], max_t, hyp.shape[2]))
+    a, a_len = _compact(hyp, bos, pad, eos, unk)
+    if remove_duplicates:
+        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
+    return (a, a_len) + _compact(ref, bos, pad, eos)
 
 
 def rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
@@ -36,16 +52,7 @@ def rouge_l_ids(hyp, ref, specials, remove_duplicates=False):
     ``rouge.rouge_l``'s of hypothesis n against reference m; an absent reference (``ref_valid`` False) reads 0 everywhere.
     ``remove_duplicates``: the compacted HYPOTHESES (not the references) go through the reference's ``remove_duplicate`` first (K33), as its
     ``save_result`` does before an answer is written or evaluated."""
-    bos, pad, eos, unk = specials
-    hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
-    if hyp.shape[0] != ref.shape[0]:
-        raise ValueError("rouge_l_ids: %d hypothesis items, %d reference items" % (hyp.shape[0], ref.shape[0]))
-    if hyp.shape[2] > ops.LCS_MAX_T:
-        raise ValueError("rouge_l_ids: hypotheses of up to %d positions (got %d)" % (ops.LCS_MAX_T, hyp.shape[2]))
-    a, a_len = _compact(hyp, bos, pad, eos, unk)
-    if remove_duplicates:
-        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
-    b, b_len = _compact(ref, bos, pad, eos)
+    a, a_len, b, b_len = _id_rows("rouge_l_ids", hyp, ref, specials, ops.LCS_MAX_T, remove_duplicates)
     lcs, f = ops.lcs_pairs(a, a_len, b, b_len)
     n = lcs.double()
     return dict(lcs=lcs, f=f, p=n / a_len.double().unsqueeze(2), r=n / b_len.clamp_min(1).double().unsqueeze(1), ref_valid=b_len.gt(0))

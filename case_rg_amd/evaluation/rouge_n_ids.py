@@ -12,7 +12,7 @@ that grows with the square of the length (K43)."""
 import torch
 
 from .. import ops
-from .rouge_ids import _compact, _pool
+from .rouge_ids import _id_rows
 
 
 def rouge_n_ids(hyp, ref, specials, max_n=2, remove_duplicates=False):
@@ -23,18 +23,9 @@ def rouge_n_ids(hyp, ref, specials, max_n=2, remove_duplicates=False):
     are the values against the present reference with the largest F, ``best_ref`` its index (the lowest among equals; -1 and zeros for an
     item without a present reference).  The orders above ``max_n`` read 0 everywhere and ``best_ref`` -1.
     ``remove_duplicates``: the compacted HYPOTHESES go through ``remove_duplicate`` first (K33), as in ``rouge_l_ids``."""
-    bos, pad, eos, unk = specials
-    hyp, ref = _pool(hyp, "hyp"), _pool(ref, "ref")
-    if hyp.shape[0] != ref.shape[0]:
-        raise ValueError("rouge_n_ids: %d hypothesis items, %d reference items" % (hyp.shape[0], ref.shape[0]))
-    if hyp.shape[2] > ops.NGRAM_MAX_T:
-        raise ValueError("rouge_n_ids: hypotheses of up to %d positions (got %d)" % (ops.NGRAM_MAX_T, hyp.shape[2]))
     if not isinstance(max_n, int) or isinstance(max_n, bool) or not 1 <= max_n <= ops.NGRAM_MAX_ORDER:
         raise ValueError("rouge_n_ids: max_n in 1..%d (got %r)" % (ops.NGRAM_MAX_ORDER, max_n))
-    a, a_len = _compact(hyp, bos, pad, eos, unk)
-    if remove_duplicates:
-        ops.remove_duplicate_ids(a.view(-1, a.shape[2]), a_len.view(-1), 3, pad)
-    b, b_len = _compact(ref, bos, pad, eos)
+    a, a_len, b, b_len = _id_rows("rouge_n_ids", hyp, ref, specials, ops.NGRAM_MAX_T, remove_duplicates)
     counts = ops.ngram_counts(a, a_len, b, b_len, max_n)
     ref_distinct = ops.ngram_distinct(b, b_len, max_n)
     out = ops.rouge_n_scores(counts["hit"], counts["distinct"], ref_distinct, b_len, max_n)

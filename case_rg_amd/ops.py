@@ -2075,7 +2075,8 @@ def _head_operands(logits, mix_logits, source_map, copies):
     return logits, mix_logits, cs, C.cast(ptrs, C.c_void_p), C.cast(lens, C.c_void_p), n, source_map.keys.shape[1]
 
 
-NGRAM_MAX_T = 256  # K32 stages a history in LDS (beside the vocabulary row in the LDS heads); K33 and the n-gram metrics stage rows as long
+ID_MAX_T = 256  # a row of token ids that one wave holds: 4 words of 64 positions (csrc/id_rows.h)
+NGRAM_MAX_T = ID_MAX_T  # K32 stages a history in LDS (beside the vocabulary row in the LDS heads); K33 and the n-gram metrics stage rows as long
 
 
 def _ban_operands(ban, rows, who, own_eos=True):
@@ -2800,7 +2801,27 @@ def sentence_compact(ids, bos, pad, eos):
 
 
 # K30 / K31: ROUGE-L on token ids and the consensus pick over a pool of candidates
-CONSENSUS_MAX_N, LCS_MAX_T = 64, 256
+CONSENSUS_MAX_N, LCS_MAX_T = 64, ID_MAX_T
+
+
+def _id_pairs(who, a, a_len, b, b_len, max_t):
+    """The operands of K30, K34 and K40, checked: a int64 [B, N, Ta] with a_len int32 [B, N], b int64 [B, M, Tb] with b_len int32 [B, M], on
+    one device, nothing empty, Ta <= max_t -> (a, a_len, b, b_len) contiguous and (B, N, M, Ta, Tb)."""
+    is_tensor = torch.is_tensor  # (spelt out, no loops: this runs in front of kernels of some 20 us)
+    if not (is_tensor(a) and is_tensor(b)) or a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or \
+            a.shape[0] != b.shape[0]:
+        raise TypeError("%s: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch" % who)
+    (B, N, Ta), (M, Tb) = a.shape, b.shape[1:]
+    if not (is_tensor(a_len) and is_tensor(b_len)) or a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or a_len.shape != (B, N) or \
+            b_len.shape != (B, M):
+        raise TypeError("%s: the lengths must be int32 [B, N] and [B, M]" % who)
+    if not a.device == a_len.device == b.device == b_len.device:
+        raise ValueError("%s: a, a_len, b and b_len must be on one device (got %s, %s, %s, %s)" % (who, a.device, a_len.device, b.device, b_len.device))
+    if B < 1 or N < 1 or M < 1 or Ta < 1 or Tb < 1:
+        raise ValueError("%s: at least one item, hypothesis, reference and position (got a %s, b %s)" % (who, list(a.shape), list(b.shape)))
+    if Ta > max_t:
+        raise ValueError("%s: hypotheses of up to %d positions (got %d)" % (who, max_t, Ta))
+    return (a.contiguous(), a_len.contiguous(), b.contiguous(), b_len.contiguous()), (B, N, M, Ta, Tb)
 
 
 def consensus_supported(N, T):
@@ -2812,15 +2833,7 @@ def lcs_pairs(a, a_len, b, b_len):
     """K30: a int64 [B, N, Ta] / a_len int32 [B, N] (front-packed hypotheses and their lengths, as ``sentence_compact`` writes them), b int64
     [B, M, Tb] / b_len int32 [B, M] (references) -> (lcs int32 [B, N, M], f f32 [B, N, M]): the LCS length and the ROUGE-L F of every pair
     (evaluation.rouge's, in f64, rounded once).  Ta <= 256; ids must lie in [0, 2^31) (not checked: they are compared on 32 bits)."""
-    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
-        raise TypeError("lcs_pairs: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
-    B, N, Ta = a.shape
-    M, Tb = b.shape[1], b.shape[2]
-    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
-        raise TypeError("lcs_pairs: the lengths must be int32 [B, N] and [B, M]")
-    if Ta > LCS_MAX_T:
-        raise ValueError("lcs_pairs: hypotheses of up to %d positions (got %d)" % (LCS_MAX_T, Ta))
-    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
+    (a, a_len, b, b_len), (B, N, M, Ta, Tb) = _id_pairs("lcs_pairs", a, a_len, b, b_len, LCS_MAX_T)
     lcs = torch.empty(B, N, M, dtype=torch.int32, device=a.device)
     f = torch.empty(B, N, M, dtype=torch.float32, device=a.device)
     A.call("case_lcs_pairs", _ptr(a), _ptr(a_len), _ptr(b), _ptr(b_len), _ptr(lcs), _ptr(f), B, N, M, Ta, Tb, _stream())
@@ -2864,12 +2877,9 @@ def ngram_supported(Ta, max_n=4):
     return 1 <= Ta <= NGRAM_MAX_T and 1 <= max_n <= NGRAM_MAX_ORDER and bool(A.lib.case_abi_features() & A.FEAT_NGRAM_COUNTS)
 
 
-def _ngram_pairs(what, a_len, b_len, max_n):
-    """The checks K34 and K35 share: the hypothesis lengths int32 [B, N], the reference lengths int32 [B, M], the order range."""
-    if not isinstance(max_n, int) or not 1 <= max_n <= NGRAM_MAX_ORDER:
+def _max_n(what, max_n):
+    if not isinstance(max_n, int) or isinstance(max_n, bool) or not 1 <= max_n <= NGRAM_MAX_ORDER:
         raise ValueError("%s: max_n in 1..%d (got %r)" % (what, NGRAM_MAX_ORDER, max_n))
-    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or a_len.dim() != 2 or b_len.dim() != 2 or a_len.shape[0] != b_len.shape[0]:
-        raise TypeError("%s: the lengths must be int32 [B, N] and [B, M]" % what)
 
 
 def ngram_counts(a, a_len, b, b_len, max_n=4):
@@ -2878,16 +2888,8 @@ def ngram_counts(a, a_len, b, b_len, max_n=4):
     above ``max_n``): clip [B, N, M, 4] (clipped k-gram matches against reference m), clip_any [B, N, 4] (against the per-k-gram maximum over
     the present references: multi-reference BLEU's numerator), hit [B, N, M, 4] / hit_any [B, N, 4] (distinct hypothesis k-grams that occur
     in reference m / in any present one), distinct [B, N, 4].  Ta <= 256; ids must lie in [0, 2^31) (not checked: compared on 32 bits)."""
-    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
-        raise TypeError("ngram_counts: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
-    B, N, Ta = a.shape
-    M, Tb = b.shape[1], b.shape[2]
-    _ngram_pairs("ngram_counts", a_len, b_len, max_n)
-    if tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
-        raise TypeError("ngram_counts: the lengths must be int32 [B, N] and [B, M]")
-    if Ta > NGRAM_MAX_T:
-        raise ValueError("ngram_counts: hypotheses of up to %d positions (got %d)" % (NGRAM_MAX_T, Ta))
-    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
+    (a, a_len, b, b_len), (B, N, M, Ta, Tb) = _id_pairs("ngram_counts", a, a_len, b, b_len, NGRAM_MAX_T)
+    _max_n("ngram_counts", max_n)
     new = lambda *shape: torch.empty(*shape, NGRAM_MAX_ORDER, dtype=torch.int32, device=a.device)  # noqa: E731
     out = dict(clip=new(B, N, M), clip_any=new(B, N), hit=new(B, N, M), hit_any=new(B, N), distinct=new(B, N))
     A.call("case_ngram_counts", _ptr(a), _ptr(a_len), _ptr(b), _ptr(b_len), _ptr(out["clip"]), _ptr(out["clip_any"]), _ptr(out["hit"]),
@@ -2901,7 +2903,9 @@ def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
     bp f64 [B, N]: the brevity penalty of ``bleu``).  evaluation.bleu.sentence_bleu's definition; ``smoothing`` "none" or "add1"."""
     if smoothing not in BLEU_SMOOTHINGS:
         raise ValueError("bleu_scores: smoothing must be 'none' or 'add1', not %r" % (smoothing,))
-    _ngram_pairs("bleu_scores", a_len, b_len, max_n)
+    _max_n("bleu_scores", max_n)
+    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or a_len.dim() != 2 or b_len.dim() != 2 or a_len.shape[0] != b_len.shape[0]:
+        raise TypeError("bleu_scores: the lengths must be int32 [B, N] and [B, M]")
     B, N = a_len.shape
     M = b_len.shape[1]
     clip, clip_any = counts["clip"], counts["clip_any"]
@@ -2920,11 +2924,6 @@ def bleu_scores(counts, a_len, b_len, max_n=4, smoothing="none"):
 # K43 / K44: the distinct k-grams of rows of any length and ROUGE-N from the counts
 def rouge_n_supported():
     return bool(A.lib.case_abi_features() & A.FEAT_ROUGE_N)
-
-
-def _max_n(what, max_n):
-    if not isinstance(max_n, int) or isinstance(max_n, bool) or not 1 <= max_n <= NGRAM_MAX_ORDER:
-        raise ValueError("%s: max_n in 1..%d (got %r)" % (what, NGRAM_MAX_ORDER, max_n))
 
 
 def ngram_distinct(b, b_len, max_n=4):
@@ -2983,7 +2982,7 @@ def rouge_n_scores(hit, hyp_distinct, ref_distinct, b_len, max_n=4):
 
 
 # K40: METEOR on token ids
-METEOR_MAX_T = 256
+METEOR_MAX_T = ID_MAX_T
 
 
 def meteor_supported(Ta):
@@ -2999,14 +2998,7 @@ def meteor(a, a_len, b, b_len, classes=None, alpha=0.9, beta=3.0, gamma=0.5, wan
     ``want_align``, align int32 [B, N, M, Ta] = the matched reference position of every hypothesis position or -1).  ``classes``: an int32 [V]
     table id -> equivalence class on the ids' device (a negative entry and an id >= V: no class) for the second stage; None: exact matches
     only.  Ta <= 256; ids must lie in [0, 2^31) (not checked: compared on 32 bits)."""
-    if a.dtype != torch.int64 or b.dtype != torch.int64 or a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0]:
-        raise TypeError("meteor: a and b must be int64 [B, N, Ta] and [B, M, Tb] of one batch")
-    B, N, Ta = a.shape
-    M, Tb = b.shape[1], b.shape[2]
-    if a_len.dtype != torch.int32 or b_len.dtype != torch.int32 or tuple(a_len.shape) != (B, N) or tuple(b_len.shape) != (B, M):
-        raise TypeError("meteor: the lengths must be int32 [B, N] and [B, M]")
-    if Ta > METEOR_MAX_T:
-        raise ValueError("meteor: hypotheses of up to %d positions (got %d)" % (METEOR_MAX_T, Ta))
+    (a, a_len, b, b_len), (B, N, M, Ta, Tb) = _id_pairs("meteor", a, a_len, b, b_len, METEOR_MAX_T)
     try:
         alpha, beta, gamma = float(alpha), float(beta), float(gamma)
     except (TypeError, ValueError):
@@ -3016,7 +3008,6 @@ def meteor(a, a_len, b, b_len, classes=None, alpha=0.9, beta=3.0, gamma=0.5, wan
     if classes is not None and (not torch.is_tensor(classes) or classes.dtype != torch.int32 or classes.dim() != 1 or classes.numel() == 0
                                 or classes.device != a.device):
         raise ValueError("meteor: classes must be a 1-D int32 tensor [V] on the ids' device")
-    a, b, a_len, b_len = (t if t.is_contiguous() else t.contiguous() for t in (a, b, a_len, b_len))
     classes = None if classes is None else classes.contiguous()
     out = dict(counts=torch.empty(B, N, M, 3, dtype=torch.int32, device=a.device),
                meteor_pair=torch.empty(B, N, M, dtype=torch.float32, device=a.device),
