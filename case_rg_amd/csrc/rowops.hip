@@ -760,12 +760,13 @@ __global__ __launch_bounds__(256) void softmax_fwd_vec_kernel(const CaseSoftmaxD
       }
     }
     m = wave_max(m);
+    const bool any = m > -INFINITY;  // admissible scores all -inf: exact zeros, as the scalar kernel gives (expf(-inf - -inf) is NaN)
     float s = 0.f;
 #pragma unroll
     for (int j = 0; j < NCH; ++j)
 #pragma unroll
       for (int e = 0; e < 8; ++e) {
-        v[j][e] = ok[j][e] ? expf(v[j][e] - m) : 0.f;
+        v[j][e] = ok[j][e] && any ? expf(v[j][e] - m) : 0.f;
         s += v[j][e];
       }
     s = wave_sum(s);

@@ -1,5 +1,6 @@
 """Bookkeeping of the exact-arithmetic GPU tests (test_gemm_exact_gpu.py, test_attention_exact_gpu.py, test_interaction_exact_gpu.py,
-test_encoder_chain_exact_gpu.py, test_additive_exact_gpu.py, test_pointer_decode_exact_gpu.py): per test function the C entry points that ran,
+test_encoder_chain_exact_gpu.py, test_additive_exact_gpu.py, test_pointer_decode_exact_gpu.py) and of test_row_ops_gpu.py
+(profiles/row_ops_parity.json): per test function the C entry points that ran,
 the cases, and the number of elements compared exactly and by a bound.  It is what profiles/exact_parity.json,
 profiles/fused_exact_parity.json and profiles/additive_exact_parity.json are made from;
 no assertion depends on it.  Nothing is written unless CASE_EXACT_LEDGER names a file."""

@@ -1340,7 +1340,7 @@ def test_multihead_attention_takes_an_arbitrary_attn_mask(dt):
         g = torch.Generator().manual_seed(4)
         fmask = (torch.randn(Lq, Lk, generator=g) * 2).to(DEV)
         bmask = (torch.rand(Lq, Lk, generator=g) < 0.3).to(DEV)
-        bmask[:, 0] = False  # no fully masked row (torch gives NaN there, so do we)
+        bmask[:, 0] = False  # no fully masked row (torch gives NaN there; ours gives exact zeros, see test_row_ops_gpu.py)
         pad = torch.zeros(N, Lk, dtype=torch.bool, device=DEV)
         pad[1, 9:] = True
         tol = 1e-3 if dt == torch.float32 else 3e-2

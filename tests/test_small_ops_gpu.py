@@ -16,6 +16,8 @@ import math
 import pytest
 import torch
 
+from row_refs import check as _check, half_ulp_bf16 as _half_ulp_bf16, tol as _tol  # noqa: F401  (shared with test_row_ops_gpu.py)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -83,34 +85,12 @@ def _counting():
         _abi.call = raw
 
 
-def _half_ulp_bf16(mag):
-    _, e = torch.frexp(mag)
-    return torch.where(mag > 0, torch.ldexp(torch.ones_like(mag), e - 9), torch.zeros_like(mag))
-
-
-def _tol(ref, f32_err, dt):
-    """f32 error bound -> bound on the stored result (plus the rounding to bf16 where the result is bf16)."""
-    f32_err = torch.zeros_like(ref) + f32_err
-    return f32_err + _half_ulp_bf16(ref.abs() + f32_err) if dt == BF16 else f32_err
-
-
 def _chain(ref, k, dt):
     return _tol(ref, k * U * ref.abs(), dt)
 
 
 def _sum(ref, n, absum, dt):
     return _tol(ref, (n + 2) * U * absum, dt)
-
-
-def _check(got, ref, tol, what):
-    assert tuple(got.shape) == tuple(ref.shape), "%s: shape %s vs %s" % (what, tuple(got.shape), tuple(ref.shape))
-    g = got.double()
-    err = (g - ref).abs()
-    bad = ~((err <= tol) | (g == ref))  # a NaN in ``got`` is bad; equal infinities are not
-    if bad.any():
-        i = int(torch.where(bad, torch.nan_to_num(err, nan=float("inf")), torch.full_like(err, -1.0)).reshape(-1).argmax())
-        raise AssertionError("%s: %d of %d elements outside the bound; flat index %d: got %r, want %r, bound %.3e" % (
-            what, int(bad.sum()), bad.numel(), i, g.reshape(-1)[i].item(), ref.reshape(-1)[i].item(), (torch.zeros_like(ref) + tol).reshape(-1)[i].item()))
 
 
 def _bits(t):
