@@ -410,7 +410,7 @@ class CaSE(nn.Module):
             raise ValueError("do_rank runs in eval mode: call model.eval() first")
         return {'rank': self._encode_select(data)[2][0]}
 
-    def do_extract(self, data, top_k=None, select="prior", labels=None):
+    def do_extract(self, data, top_k=None, select="prior", labels=None, ranking=False):
         """The supporting tokens alone (eval mode only): the encoders, the selection stage and the token-identification stage run, the
         decoder does not -> ``rank`` [B, P] (the bits of ``do_rank``); ``token_score`` f32 [B, P, L] (the stage's logits, -1e6 at PAD);
         ``token_prior`` f32 [B, P, L] (sigmoid(rank) x sigmoid(token_score) normalised over the item's P L tokens: the weights of the
@@ -419,11 +419,16 @@ class CaSE(nn.Module):
         there, PAD where the position is -1), ``support_value`` f32 [B, K] (the key there, 0 where the position is -1).  K = ``top_k``
         (None: ``self.support_top_k``), at most 256; P L <= 16384.  ``select="prior"`` ranks by ``token_prior``, ``"score"`` by
         ``token_score`` alone.  ``labels`` f32 [B, P, L] (e.g. ``token_label``): the same launch also counts, per item, ``counts`` int32
-        [B, 5] = n_valid, n_pos, n_pred (token_score > 0), tp, hits (``ops.TOKEN_COUNTS``).  Nothing is read back."""
+        [B, 5] = n_valid, n_pos, n_pred (token_score > 0), tp, hits (``ops.TOKEN_COUNTS``).  With ``labels`` and ``ranking=True`` one more
+        launch (K45, on the key ``select`` names) adds the threshold-free figures of ``evaluation.token_rank``: ``token_ap`` and
+        ``token_auc`` f64 [B], ``rank_counts`` int32 [B, 6] (``ops.TOKEN_RANK_COUNTS``) and ``best_threshold`` f32 [B].  Nothing is read
+        back."""
         if self.training:
             raise ValueError("do_extract runs in eval mode: call model.eval() first")
         if select not in ("prior", "score"):
             raise ValueError("do_extract: select must be 'prior' or 'score', not %r" % (select,))
+        if ranking and labels is None:
+            raise ValueError("do_extract: ranking=True needs labels")
         K = int(self.support_top_k if top_k is None else top_k)
         B, P, L = data['passage'].shape
         if not 1 <= K <= ops.TOKEN_MAX_K or P * L > ops.TOKEN_MAX_L:
@@ -433,14 +438,19 @@ class CaSE(nn.Module):
         token_score = se[0]
         prior = self.response_generation.token_prior(ps[0], token_score)
         flat_score = token_score.reshape(B, -1)
-        picked = ops.token_select(prior if select == "prior" else flat_score, data['passage'].ne(0).reshape(B, -1), K,
-                                  scores=None if labels is None else flat_score, labels=None if labels is None else labels.reshape(B, -1).float())
+        key, valid = prior if select == "prior" else flat_score, data['passage'].ne(0).reshape(B, -1)
+        picked = ops.token_select(key, valid, K, scores=None if labels is None else flat_score,
+                                  labels=None if labels is None else labels.reshape(B, -1).float())
         pos = picked['pos']
         ids = data['passage'].reshape(B, -1).gather(1, pos.clamp(min=0).long()).masked_fill(pos < 0, 0)
         out = {'rank': ps[0], 'token_score': token_score, 'token_prior': prior.reshape_as(token_score), 'support_pos': pos,
                'support_ids': ids, 'support_value': picked['value']}
         if labels is not None:
             out['counts'] = picked['counts']
+        if ranking:
+            ranked = ops.token_rank(key, valid, labels.reshape(B, -1).float())
+            out.update(token_ap=ranked['stats'][:, 0], token_auc=ranked['stats'][:, 1], rank_counts=ranked['counts'],
+                       best_threshold=ranked['threshold'])
         return out
 
     def forward(self, data, method='mle_train'):

@@ -164,6 +164,7 @@ SIGNATURES = {
     "case_rank_metrics": [ptr] * 8 + [i64, i64, i64, ptr],
     "case_token_labels": [ptr, ptr, ptr, i32, ptr, ptr, i64, i64, i64, i64, i64, i64, ptr],
     "case_token_select": [ptr] * 7 + [i64, i64, i32, ptr],
+    "case_token_rank": [ptr] * 6 + [i64, i64, ptr],
     "case_copy_attribution": [ptr, ptr, i64, ptr, ptr, i32, ptr, i64, ptr, ptr, i32, ptr, ptr, ptr, ptr, i64, i64, i64, ptr],
     "case_meteor": [ptr] * 5 + [i64, f64, f64, f64] + [ptr] * 5 + [i64, i64, i64, i64, i64, ptr],
     "case_pointer_head_score_stats": [ptr] * 3 + [i64, ptr, ptr, i32, ptr, i64, ptr, ptr, ptr, i64, i64, i64, ptr],
@@ -181,7 +182,7 @@ SIGNATURES = {
 
 # Entry points added after the 32-bit feature mask filled up: an older build of the same ABI generation may lack them, so they are bound
 # where the library exports them and asked for by name (``has``) instead of by feature bit
-OPTIONAL = ("case_pointer_head_loss", "case_pointer_head_loss_bwd")
+OPTIONAL = ("case_pointer_head_loss", "case_pointer_head_loss_bwd", "case_token_rank")
 
 
 def _load():

@@ -478,35 +478,51 @@ class CumulativeTrainer(object):
                     gen_share=ratio(sums["gen_share"], tokens), context_share=ratio(sums["context_share"], tokens),
                     passage_share=ratio(sums["passage_share"], tokens), items=items, tokens=tokens)
 
-    def evaluate_extract(self, dataset, collate_fn, batch_size, top_k=None, select="prior", labels="token_label"):
+    def evaluate_extract(self, dataset, collate_fn, batch_size, top_k=None, select="prior", labels="token_label", ranking=False):
         """Token-level metrics of the supporting-token stage: ``model.do_extract(data, top_k, select, labels=data[labels])`` per batch (K38
         counts the items while it selects their tokens), the column sums kept on the device, one read-back at the end -> dict(precision =
         tp / n_pred and recall = tp / n_pos of the tokens whose logit is positive, f1 = their harmonic mean, precision_at_k = hits /
         sum of min(K, n_valid) and recall_at_k = hits / n_pos of the K tokens ``select`` ranks first, items, tokens = the non-PAD tokens
         counted); micro-averages over tokens, 0.0 where a denominator is 0.  Where ``data`` lacks ``labels`` they come from
-        ``model.label_batch(data)`` (K37; ``set_token_freq`` first).  One process, under no_grad in eval mode; the model's mode is restored
-        afterwards."""
+        ``model.label_batch(data)`` (K37; ``set_token_freq`` first).  ``ranking=True`` (K45, one more launch per batch, on the key
+        ``select`` names) adds the threshold-free figures of ``evaluation.token_rank``: map = the mean AP over the items with a positive
+        (ranked_items), auc = the mean AUC over the items with both classes (auc_items), auc_stratified = sum auc_num2 / sum 2 n_pos n_neg
+        (the within-item pair-weighted figure), oracle_f1 = 2 sum best_tp / sum (best_n + n_pos) (the pooled F1 when every item is cut
+        where its own F1 peaks: no threshold does better on any single item); their sums ride in f64 beside the counts, so the evaluation
+        keeps its one read-back.  One process, under no_grad in eval mode; the model's mode is restored afterwards."""
+        from ..evaluation.token_rank import rank_sums, summarize_rank
         was_training = self.model.training
         self.model.eval()
-        total, items = None, 0
+        total, rank_total, items = None, None, 0
         try:
             with torch.no_grad():
                 loader = torch.utils.data.DataLoader(dataset, collate_fn=collate_fn, batch_size=batch_size, shuffle=False,
                                                      pin_memory=torch.cuda.is_available())
                 for data in DevicePrefetcher(loader):
                     gold = data[labels] if labels in data else self.model.label_batch(data)['token_label']
-                    counts = self.model.do_extract(data, top_k=top_k, select=select, labels=gold)['counts'].long()
+                    got = self.model.do_extract(data, top_k=top_k, select=select, labels=gold, ranking=ranking)
+                    counts = got['counts'].long()
                     K = self.model.support_top_k if top_k is None else int(top_k)
                     part = torch.cat([counts.sum(0), counts[:, 0].clamp(max=K).sum().reshape(1)])
                     total = part if total is None else total + part
+                    if ranking:
+                        part = rank_sums(torch.stack([got['token_ap'], got['token_auc']], dim=1), got['rank_counts'])
+                        rank_total = part if rank_total is None else rank_total + part
                     items += counts.shape[0]
         finally:
             self.model.train(was_training)
-        names = ("precision", "recall", "f1", "precision_at_k", "recall_at_k")
+        names = ("precision", "recall", "f1", "precision_at_k", "recall_at_k") + (("map", "auc", "auc_stratified", "oracle_f1") if ranking else ())
         if items == 0:
-            return dict({name: float('nan') for name in names}, items=0, tokens=0)
-        n_valid, n_pos, n_pred, tp, hits, slots = total.tolist()  # (the one read-back of the evaluation)
+            return dict({name: float('nan') for name in names}, items=0, tokens=0, **(dict(ranked_items=0, auc_items=0) if ranking else {}))
+        if ranking:  # (the counts are far below 2^53: exact in f64)
+            sums = torch.cat([total.double(), rank_total]).tolist()  # (the one read-back of the evaluation)
+            n_valid, n_pos, n_pred, tp, hits, slots = (int(v) for v in sums[:6])
+        else:
+            n_valid, n_pos, n_pred, tp, hits, slots = total.tolist()  # (the one read-back of the evaluation)
         ratio = lambda a, b: a / b if b else 0.0  # noqa: E731
         precision, recall = ratio(tp, n_pred), ratio(tp, n_pos)
-        return dict(precision=precision, recall=recall, f1=ratio(2 * precision * recall, precision + recall),
-                    precision_at_k=ratio(hits, slots), recall_at_k=ratio(hits, n_pos), items=items, tokens=n_valid)
+        out = dict(precision=precision, recall=recall, f1=ratio(2 * precision * recall, precision + recall),
+                   precision_at_k=ratio(hits, slots), recall_at_k=ratio(hits, n_pos), items=items, tokens=n_valid)
+        if ranking:
+            out.update(summarize_rank(sums[6:]))
+        return out

@@ -5,7 +5,8 @@ The stage's logits stay where ``CaSE.do_extract`` left them -- ``token_score`` [
 
 A token is predicted where its logit is positive (sigmoid > 0.5) and labelled where its label exceeds 0.5; only valid (non-PAD) positions
 count.  ``hits`` are the labelled tokens among the K selected ones, where the selection key (``select``) may differ from the logits, e.g.
-``token_prior``.  Average precision and AUC over tokens are not computed.  Limits: P x L <= 16384 positions per item, K <= 256."""
+``token_prior``.  Average precision, AUC and the best F1 cut over tokens are in ``token_rank`` (K45).  Limits: P x L <= 16384 positions per
+item, K <= 256."""
 import torch
 
 from .. import ops

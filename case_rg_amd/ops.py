@@ -3131,6 +3131,46 @@ def token_select(values, valid, k, scores=None, labels=None):
     return out
 
 
+# K45: the threshold-free ranking figures of a row of token scores (evaluation/token_rank.py states the definitions)
+TOKEN_RANK_COUNTS = ("n_valid", "n_pos", "auc_num2", "best_tp", "best_n", "n_groups")  # the columns of ``counts``
+TOKEN_RANK_STATS = ("ap", "auc")  # the columns of ``stats``
+
+
+def token_rank_supported():
+    return A.has("case_token_rank")
+
+
+def token_rank(scores, valid, labels):
+    """K45: scores f32 [B, S] (one item per row), valid bool [B, S] or None (all), labels float [B, S] (positive where > 0.5) ->
+    dict(stats f64 [B, 2] = ap, auc; counts int32 [B, 6] in ``TOKEN_RANK_COUNTS``' order; threshold f32 [B] = the score of the best-F1 group,
+    +inf where the item has no positive).  Scores compare as K38's key (NaN as -inf, -0.0 == +0.0); every figure is a function of the
+    groups of equal key, so none depends on the position of a token.  S <= 16384; ValueError for a longer row, a shape or dtype mismatch or
+    tensors off the device.  No autograd, nothing is read back."""
+    if not torch.is_tensor(scores) or scores.dtype != torch.float32 or scores.dim() != 2:
+        raise ValueError("token_rank: scores must be an f32 [B, S] tensor")
+    B, S = scores.shape
+    if valid is not None and (not torch.is_tensor(valid) or valid.dtype not in (torch.bool, torch.uint8) or tuple(valid.shape) != (B, S)):
+        raise ValueError("token_rank: valid must be bool [%d, %d] or None" % (B, S))
+    if not torch.is_tensor(labels) or not labels.is_floating_point() or tuple(labels.shape) != (B, S):
+        raise ValueError("token_rank: labels must be float [%d, %d]" % (B, S))
+    if S < 1 or S > TOKEN_MAX_L:
+        raise ValueError("token_rank: rows of 1 .. %d positions (got %d)" % (TOKEN_MAX_L, S))
+    if not token_rank_supported():
+        raise RuntimeError("token_rank: this build of the library lacks K45 (case_token_rank) -- rebuild it (make -C case_rg_amd/csrc)")
+    for name, t in (("scores", scores), ("valid", valid), ("labels", labels)):
+        if t is not None and (t.device.type != "cuda" or t.device != scores.device):
+            raise ValueError("token_rank: %s must live on the device (%s; scores on %s)" % (name, t.device, scores.device))
+    scores = scores if scores.is_contiguous() else scores.contiguous()
+    labels = labels.float().contiguous()
+    valid = None if valid is None else valid.contiguous()
+    stats = torch.empty(B, len(TOKEN_RANK_STATS), dtype=torch.float64, device=scores.device)
+    counts = torch.empty(B, len(TOKEN_RANK_COUNTS), dtype=torch.int32, device=scores.device)
+    threshold = torch.empty(B, dtype=torch.float32, device=scores.device)
+    if B:
+        A.call("case_token_rank", _ptr(scores), _ptr(_u8(valid)), _ptr(labels), _ptr(stats), _ptr(counts), _ptr(threshold), B, S, _stream())
+    return dict(stats=stats, counts=counts, threshold=threshold)
+
+
 # K39: where the pointer mass of a target token comes from (the per-segment split, the best source position, the run length).  "auto": a
 # device-sorted source map and <= 4 memories; "off": the host form (evaluation.attribution.copy_attribution_host) wherever a pass attributes.
 COPY_ATTRIBUTION = os.environ.get("CASE_COPY_ATTRIBUTION", "auto")

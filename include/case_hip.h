@@ -910,6 +910,26 @@ int case_token_select(const float* values, const uint8_t* valid, const float* sc
                       int32_t* counts, int64_t B, int64_t S, int32_t K, case_stream_t stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Threshold-free ranking metrics of the supporting-token stage (no feature bit: the 32-bit mask is full, so ask the library for the
+ * symbol; purely additive, generation 600 unchanged).  evaluation/token_rank.py states the definitions.
+ * K45 case_token_rank: every row of scores f32 [B, S] is one item; valid u8 [B, S] (NULL: all) says which positions hold a token, a valid
+ *   position is positive where labels f32 [B, S] exceeds 0.5.  Scores compare as K38's key (-0.0 == +0.0, NaN as -inf); the valid
+ *   positions fall into groups of equal key, g = 1 .. G from the highest key down, with tp_g / n_g the positives / positions through group g.
+ *   No figure depends on the order inside a group, hence none on where in the row a token sits.
+ *     counts[b, :] int32 x 6: n_valid, n_pos, auc_num2 = sum_g pos_g (2 (n_neg - negcum_g) + neg_g), best_tp, best_n (tp_g and n_g of the
+ *                  lowest g that maximises 2 tp_g / (n_g + n_pos), fractions compared exactly), n_groups
+ *     stats[b, :]  f64 x 2: ap = (1 / n_pos) sum_g (tp_g - tp_{g-1}) tp_g / n_g (0 where n_pos == 0); auc = auc_num2 / (2 n_pos n_neg), one
+ *                  division of exact integers (0 where n_pos n_neg == 0)
+ *     threshold[b] f32: the score of the best group in canonical form (+0.0 for either zero, -inf for NaN); n_pos == 0: best_tp = best_n
+ *                  = 0 and +inf
+ *   One workgroup per item sorts the row's (key, label) pairs in LDS (8 bytes per position of the row length padded to a power of two,
+ *   128 KiB at 16384); every AP term is rounded once and summed through a tree of fixed shape, no atomics: two launches give the same bits.
+ *   S <= 16384, or CASE_E_UNSUPPORTED; B == 0 returns without a launch.  Asynchronous on `stream`; every output element is written.
+ * ------------------------------------------------------------------------------------------- */
+int case_token_rank(const float* scores, const uint8_t* valid, const float* labels, double* stats, int32_t* counts, float* threshold,
+                    int64_t B, int64_t S, case_stream_t stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Answer attribution (CASE_FEAT_COPY_ATTRIBUTION; purely additive, generation 600 unchanged).
  * K39 case_copy_attribution: where the pointer mass of a target comes from.  Operands as in K29 (case_pointer_head_score) without the logits:
  *   mix_logits [R, 1 + nmem] f32, keys [R / rows_per_source, S] (row r reads key row r / rows_per_source), copies / lens with R rows and
